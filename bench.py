@@ -7,6 +7,12 @@ Single GPU:   python bench.py --gpus 1 --steps 20 --warmup 3
 Multi GPU:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                   --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times K generations and prints one JSON
+result line (`ms_per_step` = milliseconds per timed generation).
+`--dump-outputs DIR` additionally writes what the last timed generation
+computed as DIR/<name>.npy; `--full` is where any measurement beyond the
+headline figure belongs (none today).
+
 Weak scaling: each rank owns a fixed per-GPU sub-population (default 4000)
 sampled with counter-based philox streams; the centered ranking is global
 (one all-gather of N floats) and the (mu, sigma) gradient merge is one
@@ -45,7 +51,42 @@ def parse_args():
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--policy", choices=["linear", "mlp64"], default="linear",
                    help="linear = Humanoid-v4 linear policy (the headline metric); mlp64 = the paper's MLP-64-tanh brax config")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (center, stdev, mean_eval, "
+                        "and the generation's fitness vector) as DIR/<name>.npy; same arguments => same inputs, "
+                        "so two builds can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure; a plain run only sets up, warms up, "
+                        "times the steps and prints the result line (there are no extra measurements today, so "
+                        "this changes nothing yet)")
     return p.parse_args()
+
+
+def dump_outputs(directory, searcher, problem):
+    """Write what a caller of `searcher.step()` holds after the last timed
+    step: the updated search distribution (status center/stdev), the
+    generation's mean fitness, and the generation's global fitness vector
+    (the rollout kernel's direct output, read from the problem's reused
+    sampling batch; rank-local rows when world > 1). A few tens of KB."""
+    import numpy as np
+
+    def to_numpy(x):
+        t = torch.as_tensor(x).detach().to("cpu")
+        t = torch.Tensor.as_subclass(t, torch.Tensor)
+        return t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+
+    status = searcher.status
+    arrays = {
+        "center": to_numpy(status["center"]),
+        "stdev": to_numpy(status["stdev"]),
+        "mean_eval": np.asarray(status["mean_eval"], dtype=np.float64),
+    }
+    batch = getattr(problem, "_grad_batch_cache", None)
+    if batch is not None:
+        arrays["fitnesses"] = to_numpy(batch._evals[:, searcher.obj_index])
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), arr)
 
 
 def main():
@@ -113,6 +154,9 @@ def main():
 
     solutions_per_sec = (total_popsize * args.steps) / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, searcher, problem)
 
     if rank == 0:
         result = {

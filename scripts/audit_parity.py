@@ -1,4 +1,4 @@
-"""Executable parity audit vs the reference tree (read-only mount):
+"""Executable parity audit vs the reference's public names:
 
 1. AST sweep: every public class/function defined in the reference's
    modules must resolve to an attribute somewhere in evotorch_amd's
@@ -8,17 +8,23 @@
 3. Constructor sweep: every reference constructor keyword of the searcher
    and problem classes must be accepted here.
 
-Exit code 0 = parity holds. Run: python scripts/audit_parity.py
+The reference's names are stored in tests/golden/reference_api.json, so the
+audit needs no reference tree; `--record REF_PKG` re-reads them from the
+reference's package directory. Exit code 0 = parity holds.
+Run: python scripts/audit_parity.py
 """
 
 import ast
 import importlib
 import inspect
+import json
 import os
 import sys
 
-REF = "/root/reference/src/evotorch"
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden", "reference_api.json")
+REF = sys.argv[2] if sys.argv[1:2] == ["--record"] else None  # None: use the stored names
+sys.path.insert(0, REPO)
 
 EXCUSED = {
     # Ray actor machinery: replaced by the RCCL SPMD layer (parallel/)
@@ -51,10 +57,35 @@ def public_defs():
     return out
 
 
+def class_defs(rel, klass):
+    """(public method names, constructor keywords) of a reference class."""
+    methods, kwargs = [], []
+    tree = ast.parse(open(os.path.join(REF, rel)).read())
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ClassDef) and node.name == klass:
+            for item in node.body:
+                if isinstance(item, ast.FunctionDef) and not item.name.startswith("_"):
+                    methods.append(item.name)
+                if isinstance(item, ast.FunctionDef) and item.name == "__init__":
+                    kwargs += [a.arg for a in item.args.args + item.args.kwonlyargs if a.arg != "self"]
+    return methods, kwargs
+
+
 def main():
-    if not os.path.isdir(REF):
-        print("reference tree not mounted; nothing to audit")
-        return 0
+    if REF is None:
+        with open(GOLDEN) as f:
+            stored = json.load(f)
+    elif not os.path.isdir(REF):
+        sys.exit(f"reference package not found at {REF}")
+    else:
+        stored = {}
+
+    def names(key, collect):
+        """The reference's names under `key`: collected from its tree when
+        recording, read from the stored file otherwise."""
+        if REF is not None:
+            stored[key] = collect()
+        return stored[key]
 
     import evotorch_amd as ea
 
@@ -71,8 +102,8 @@ def main():
 
     failures = []
     total = 0
-    for relpath, names in public_defs().items():
-        for n in names:
+    for relpath, defs in sorted(names("public_defs", public_defs).items()):
+        for n in defs:
             total += 1
             if n in EXCUSED:
                 continue
@@ -94,17 +125,15 @@ def main():
     ]
     ray_methods = {"actor_index", "actors", "all_remote_envs", "all_remote_problems", "is_remote",
                    "kill_actors", "num_actors", "put_ray_object", "remote_hook", "storage", "untyped_storage"}
+    n_methods = 0
     for rel, klass, mine in method_pairs:
-        tree = ast.parse(open(os.path.join(REF, rel)).read())
-        for node in ast.walk(tree):
-            if isinstance(node, ast.ClassDef) and node.name == klass:
-                for item in node.body:
-                    if isinstance(item, ast.FunctionDef) and not item.name.startswith("_"):
-                        if item.name in ray_methods:
-                            continue
-                        if not hasattr(mine, item.name):
-                            failures.append(f"method missing: {klass}.{item.name}")
-    print("method sweep done")
+        for method in names(f"methods/{klass}", lambda: class_defs(rel, klass)[0]):
+            n_methods += 1
+            if method in ray_methods:
+                continue
+            if not hasattr(mine, method):
+                failures.append(f"method missing: {klass}.{method}")
+    print(f"method sweep done: {n_methods} reference methods")
 
     ctor_pairs = [
         ("core.py", "Problem", ea.Problem),
@@ -119,17 +148,26 @@ def main():
         ("neuroevolution/supervisedne.py", "SupervisedNE", ea.neuroevolution.SupervisedNE),
         ("neuroevolution/vecgymne.py", "VecGymNE", ea.neuroevolution.VecGymNE),
     ]
+    n_kwargs = 0
     for rel, klass, mine in ctor_pairs:
-        tree = ast.parse(open(os.path.join(REF, rel)).read())
         my_params = set(inspect.signature(mine.__init__).parameters)
-        for node in ast.walk(tree):
-            if isinstance(node, ast.ClassDef) and node.name == klass:
-                for item in node.body:
-                    if isinstance(item, ast.FunctionDef) and item.name == "__init__":
-                        for a in item.args.args + item.args.kwonlyargs:
-                            if a.arg != "self" and a.arg not in my_params:
-                                failures.append(f"ctor kwarg missing: {klass}({a.arg}=...)")
-    print("ctor sweep done")
+        for kwarg in names(f"ctor_kwargs/{klass}", lambda: class_defs(rel, klass)[1]):
+            n_kwargs += 1
+            if kwarg not in my_params:
+                failures.append(f"ctor kwarg missing: {klass}({kwarg}=...)")
+    print(f"ctor sweep done: {n_kwargs} reference keywords")
+    if total == 0 or n_methods == 0 or n_kwargs == 0:
+        failures.append("the reference's names are empty")
+
+    if REF is not None:  # one line per module / class keeps the stored file short
+        def block(d, pad):
+            return "{\n" + ",\n".join(
+                f"{pad} {json.dumps(k)}: {block(v, pad + ' ') if isinstance(v, dict) else json.dumps(v)}"
+                for k, v in sorted(d.items())) + f"\n{pad}}}"
+
+        with open(GOLDEN, "w") as f:
+            f.write(block(stored, "") + "\n")
+        print("recorded the reference's names to tests/golden/reference_api.json")
 
     for f in failures:
         print("FAIL", f)

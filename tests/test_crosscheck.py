@@ -1,15 +1,13 @@
 """Numerical cross-validation against the reference implementation, run as
-part of the CPU suite when the reference tree is present (it is mounted
-read-only in the build environment; users without it skip)."""
+part of the CPU suite. The reference's outputs and public names are stored
+under tests/golden/ (recorded by the two scripts' --record mode), so the
+checks need no reference tree."""
 
 import os
 import subprocess
 import sys
 
-import pytest
 
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference tree not mounted")
 def test_gradients_match_reference():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     result = subprocess.run(
@@ -18,9 +16,9 @@ def test_gradients_match_reference():
     )
     assert result.returncode == 0, result.stdout[-3000:] + result.stderr[-2000:]
     assert "all within 1e-6 of the reference" in result.stdout
+    assert result.stdout.count("\nOK ") + result.stdout.startswith("OK ") == 31, result.stdout[-3000:]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference tree not mounted")
 def test_symbol_method_ctor_parity():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     result = subprocess.run(
@@ -29,3 +27,4 @@ def test_symbol_method_ctor_parity():
     )
     assert result.returncode == 0, result.stdout[-3000:] + result.stderr[-1500:]
     assert "parity holds" in result.stdout
+    assert "symbol sweep: 252 reference defs, 0 missing" in result.stdout

@@ -4,6 +4,7 @@ tests/test_examples.py integration strategy)."""
 import os
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -28,13 +29,20 @@ CASES = [
 
 @pytest.mark.parametrize("script,args", CASES, ids=[c[0] for c in CASES])
 def test_example_runs(script, args, tmp_path):
-    result = subprocess.run(
-        [sys.executable, os.path.join(REPO, script), *args],
-        cwd=tmp_path,  # checkpoints etc. land in a temp dir
-        capture_output=True,
-        text=True,
-        timeout=420,
-    )
+    # An example that writes a fixed name into the system temp dir gets a
+    # private one, instead of meeting a file another user left there. It sits
+    # directly under the system temp dir, not under tmp_path: multiprocessing
+    # binds AF_UNIX sockets below TMPDIR, and their paths are limited to ~100
+    # characters.
+    with tempfile.TemporaryDirectory(prefix="ex") as private_tmp:
+        result = subprocess.run(
+            [sys.executable, os.path.join(REPO, script), *args],
+            cwd=tmp_path,  # checkpoints etc. land in a temp dir
+            env={**os.environ, "TMPDIR": private_tmp},
+            capture_output=True,
+            text=True,
+            timeout=420,
+        )
     assert result.returncode == 0, f"{script} failed:\n{result.stderr[-2000:]}"
 
 
@@ -59,3 +67,34 @@ def test_bench_json_contract():
     assert d["value"] > 0 and d["ms_per_step"] > 0
     assert d["scaling"] in ("weak", "strong")
     assert isinstance(d["config"], dict) and "model" in d["config"]
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float .npy
+    arrays; the same arguments give the same inputs, so two runs agree
+    exactly on CPU. --full is accepted and keeps the result line."""
+    import json
+
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+             "--popsize-per-gpu", "16", "--episode-length", "5", "--dump-outputs", str(tmp_path / name), *extra],
+            capture_output=True, text=True, timeout=600,
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads(out.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["center.npy", "fitnesses.npy", "mean_eval.npy", "stdev.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    assert a["center.npy"].shape == (6409,) and a["stdev.npy"].shape == (6409,)
+    assert a["fitnesses.npy"].shape == (16,) and a["mean_eval.npy"].shape == ()
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64)
+        assert np.isfinite(a[f]).all()
+        assert np.array_equal(a[f], b[f]), f
+    assert sum(arr.nbytes for arr in a.values()) <= 64 * 1024 * 1024
