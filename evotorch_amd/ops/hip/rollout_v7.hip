@@ -7,20 +7,41 @@
 // population, i.e. real GEMMs once many members sit in one block:
 //
 //   h(M×16)    = obs(M×384) @ Vᵀ(384×16)          GEMM1 on mfma
-//   o'(M×384)  = [h|act](M×64) @ [U;D2](64×384)    GEMM2 on mfma
+//   o'(M×384)  = [h|act](M×32) @ [U;D2](32×384)    GEMM2 on mfma
 //
-// run on v_mfma_f32_16x16x32_bf16. The per-member policy GEMV
-// (act = W·obsn, no shared operand — not MFMA-shaped) keeps per-member
-// weights in REGISTERS (one 32-lane half-wave per member, 12 obs columns
-// per lane, 17 accumulators, DPP-reduced on the VALU pipe).
+// run on v_mfma_f32_16x16x32_bf16 (GEMM2 with K = 32 exactly: 16 h rows
+// + 16 action rows; the 17th action is a rank-1 epilogue term).
 //
-// Occupancy (the v7.2→v7.3 lesson, measured via SQ_WAIT_ANY:SQ_BUSY ≈ 5:1):
-// a single 8-wave block per CU exposes every barrier and LDS-latency chain
-// of the 1000-step loop — there is nothing else to run. v7.3 uses 4-wave
-// (256-thread) blocks of 8 members with ≤ 80 KB LDS and ≤ 256 VGPRs, so
-// TWO independent blocks share each CU and cover each other's stalls; the
-// GEMM2 B-operand ([U;D2]) lives in register fragments (48 VGPRs), the
-// GEMM1 B-operand (V) in LDS.
+// Blocks: 2·kWaves members on kWaves waves. The default is ONE 8-wave
+// block of 16 members per CU; EVOTORCH_AMD_ROLLOUT_V7_WAVES=4 selects
+// 4-wave blocks of 8 members, two of which share a CU (measured neutral
+// or worse, kept as a probe). All MFMA operands live in LDS: V (GEMM1 B),
+// [U;D2] k-major (GEMM2 B) — register fragments for them would push the
+// kernel past 256 VGPRs and demote the policy weights to scratch.
+//
+// Policy phase (act = clamp(W·obsn + b), no shared operand — not
+// MFMA-shaped): per-member weights stay in REGISTERS, one 32-lane
+// half-wave per member, 12 obs columns per lane, 17 accumulators of
+// v_dot2. Actions 0..15 are then reduced with a TRANSPOSING butterfly on
+// the VALU pipe: each level a lane keeps half of its accumulators and
+// hands the other half to a partner (16→8→4→2→1 over lane^1, lane^2,
+// lane^4, lane^8 with DPP quad_perm / row_shl+row_shr / row_ror, then one
+// v_permlane16_swap add across the two rows), so 16 lanes end up with one
+// finished action each — ~50 ops instead of 16 × 5 full-width DPP adds,
+// in the same summation tree. Action 16 keeps a plain 5-step DPP reduce
+// into lane 31. The tail (bias, clamp, bf16 convert, hact store) then runs
+// ONCE on those 17 lanes, lane-parallel. The tail lanes also publish the
+// fp32 actions, and after the barrier the half-wave folds them into Σa² as
+// one fma chain in action order, sliced under the GEMM2 epilogue. No ds_bpermute shuffles in the
+// loop (see reduce32_dpp).
+//
+// GEMM2 phase: hact is the MFMA A operand, [U;D2] the B operand; a lane's
+// D fragment is one obs column of four members.
+//
+// Every sum keeps the order it had before the transposing reduction, so
+// results are bit-identical to the full-width version; and a member's
+// arithmetic never depends on its slot (half-wave, wave or block):
+// results are bitwise invariant under member_offset sharding.
 //
 // LDS row strides are padded (OPS = OP+8, KS = 72) — the natural 768 B /
 // 128 B strides are ≡ 0 (mod 64 dwords), serializing 16-row fragment
@@ -75,6 +96,13 @@ __device__ __forceinline__ float dpp_add(float x) {
     return x + __builtin_bit_cast(float, moved);
 }
 
+// x + (y moved across lanes by DPP control kCtrl)
+template <int kCtrl>
+__device__ __forceinline__ float dpp_add_from(float x, float y) {
+    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), kCtrl, 0xf, 0xf, true);
+    return x + __builtin_bit_cast(float, moved);
+}
+
 __device__ __forceinline__ float reduce32_dpp(float x) {
     x = dpp_add<0x111>(x);  // row_shr:1
     x = dpp_add<0x112>(x);  // row_shr:2
@@ -82,6 +110,40 @@ __device__ __forceinline__ float reduce32_dpp(float x) {
     x = dpp_add<0x118>(x);  // row_shr:8
     x = dpp_add<0x142>(x);  // row_bcast:15 → lanes 31/63 hold the 32-lane sums
     return x;
+}
+
+// One level of the transposing (halving) reduction inside a 16-lane DPP
+// row. A lane holds two partial sums, lo and hi; it keeps one of them
+// (hi when `up`, else lo), hands the other to its partner lane and adds
+// the partner's partial of the sum it kept. kCtrl must pair every lane
+// with a lane whose `up` is the opposite.
+template <int kCtrl>
+__device__ __forceinline__ float dpp_halve(float lo, float hi, bool up) {
+    const float keep = up ? hi : lo;
+    const float send = up ? lo : hi;
+    return dpp_add_from<kCtrl>(keep, send);
+}
+
+// The level for partner lane^4, which no single DPP control reaches:
+// banks 0/2 of a row (lanes 0-3, 8-11) read lane+4, banks 1/3 lane-4.
+__device__ __forceinline__ float dpp_halve_xor4(float lo, float hi, bool up) {
+    const float keep = up ? hi : lo;
+    const int send = __builtin_bit_cast(int, up ? lo : hi);
+    int moved = __builtin_amdgcn_update_dpp(0, send, 0x104, 0xf, 0x5, false);  // row_shl:4
+    moved = __builtin_amdgcn_update_dpp(moved, send, 0x114, 0xf, 0xa, false);  // row_shr:4
+    return keep + __builtin_bit_cast(float, moved);
+}
+
+// Sum of the two 16-lane rows of a half-wave, in both rows:
+// v_permlane16_swap exchanges the odd rows of its first operand with the
+// even rows of its second, leaving row 0's x in one result and row 1's in
+// the other.
+__device__ __forceinline__ float row_pair_add(float x) {
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    // scalars first: __builtin_bit_cast applied to r[1] directly reads r[0]
+    const unsigned from_row0 = r[0], from_row1 = r[1];
+    return __builtin_bit_cast(float, from_row0) + __builtin_bit_cast(float, from_row1);
 }
 
 struct RolloutV7Args {
@@ -109,6 +171,7 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
     constexpr int OPS = OP + 8;               // padded obs-row stride (bank decorrelation)
     constexpr int KS = 72;                    // padded hact row stride (vs 64)
     constexpr int A_MAX = A;
+    constexpr int AF = (A_MAX + 1 + 3) / 4 * 4;  // actf_l row stride (16-byte rows)
     constexpr int R = 16;
     constexpr int kTiles = OP / 16;           // GEMM2 output tiles
     constexpr int kTilesPerWave = kTiles / kWaves;
@@ -126,14 +189,13 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
     __bf16* obsn_l = obs_l + kM * OPS;                   // [kM][OPS] normalized obs
     __bf16* hact_l = obsn_l + kM * OPS;                  // [16][KS]: k<16 h, k=16..31 act[0..16), slot 32 = act[16]
     __bf16* v_l = hact_l + 16 * KS;                      // [16][OPS] V (GEMM1 B-operand)
-    float* b_l = reinterpret_cast<float*>(v_l + 16 * OPS);  // [kM][A_MAX] bias
-    float* c_l = b_l + kM * A_MAX;                       // [OP]
+    float* actf_l = reinterpret_cast<float*>(v_l + 16 * OPS);  // [kM][AF] fp32 actions of the step; slot A_MAX: Σa² at wrap-up
+    float* c_l = actf_l + kM * AF;                       // [OP]
     float* wr_l = c_l + OP;                              // [OP]
     float* mean_l = wr_l + OP;                           // [OP]
     float* istd_l = mean_l + OP;                         // [OP]
     float* wave_fit = istd_l + OP;                       // [kWaves][16] fitness partials
-    float* actsq_l = wave_fit + kWaves * 16;             // [kM]
-    float* d2last_l = actsq_l + kM;                      // [OP] D2_T row A-1 (rank-1 epilogue term)
+    float* d2last_l = wave_fit + kWaves * 16;            // [OP] D2_T row A-1 (rank-1 epilogue term)
     __bf16* ud_l = reinterpret_cast<__bf16*>(d2last_l + OP);  // [OP][40] k-major GEMM2 B
 
     const long RO = (long)R * O, AO = (long)A * O;
@@ -157,11 +219,7 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
         d2last_l[j] = in ? b2f7(f2b7(eD2[(long)(A - 1) * O + j])) : 0.0f;
     }
     for (int j = tid; j < 16 * KS; j += kThreads) hact_l[j] = f2b7(0.0f);
-    for (int j = tid; j < kM * A_MAX; j += kThreads) {
-        const int m = j / A_MAX, a = j % A_MAX;
-        b_l[j] = (m < live && a < A) ? args.params[(long)(base_member + m) * (AO + A) + AO + a] : 0.0f;
-    }
-    if (tid < kM) actsq_l[tid] = 0.0f;
+    for (int j = tid; j < kM * AF; j += kThreads) actf_l[j] = 0.0f;
 
     // GEMM1 B (V) in LDS (only wave 0 reads it — registers on every wave
     // would blow the VGPR budget and demote w_frag to scratch).
@@ -212,6 +270,17 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
         }
     }
 
+    // After the transposing reduction (see the policy phase) the first 16
+    // lanes of the half-wave hold one finished action each; its lane 31
+    // holds action A-1 from the plain reduction. Those 17 lanes run the tail.
+    const bool up0 = lane & 1, up1 = lane & 2, up2 = lane & 4, up3 = lane & 8;
+    const int my_act = (l32 == 31) ? 16 : ((up0 ? 8 : 0) + (up1 ? 4 : 0) + (up2 ? 2 : 0) + (up3 ? 1 : 0));
+    const bool tail_lane = my_member < live && my_act < A && (l32 < 16 || l32 == 31);
+    const float my_bias =
+        tail_lane ? args.params[(long)(base_member + my_member) * (AO + A) + AO + my_act] : 0.0f;
+    __bf16* my_hact = hact_l + my_member * KS + ((my_act < 16) ? (16 + my_act) : 32);
+    float* my_actf = actf_l + my_member * AF + my_act;
+
     // ---- initial observations (philox stream per global member) -------------
     for (int j = tid; j < kM * OPS; j += kThreads) obs_l[j] = f2b7(0.0f);
     __syncthreads();
@@ -240,7 +309,7 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
 
     // ---- episode state in registers ----
     float fit_part[4] = {0.f, 0.f, 0.f, 0.f};  // member rows (lane>>4)*4+reg of GEMM2
-    float actsq_total = 0.0f;                  // on l32==31 lanes: my_member's Σa²
+    float actsq_total = 0.0f;                  // my_member's Σa² (lane 31 of the half-wave publishes it)
     float stat_sum[kTilesPerWave] = {};        // per owned obs column
     float stat_sumsq[kTilesPerWave] = {};
 
@@ -285,17 +354,31 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
                     }
                 }
             }
+            // Transposing reduction of actions 0..15 over the half-wave's
+            // 32 lanes: every level halves the accumulators a lane still
+            // carries (16→8→4→2→1) while it doubles the lanes summed into
+            // them, ~50 VALU ops instead of 16 × 5 full-width adds. The
+            // levels pair lane^1, lane^2, lane^4, lane^8 and finally the
+            // two rows — the same balanced tree, pair for pair, as the
+            // row_shr 1/2/4/8 + row_bcast reduction action 16 still uses,
+            // so every action sum has one summation order (and the bits
+            // the full-width reduction gave). A lane of either row ends
+            // up with action 8·bit0 + 4·bit1 + 2·bit2 + bit3 = my_act.
+            // Identical in both half-waves and every wave, so a member's
+            // arithmetic does not depend on its slot.
+            float v8[8], v4[4], v2[2];
 #pragma unroll
-            for (int a = 0; a < A_MAX; ++a) acc[a] = reduce32_dpp(acc[a]);
-            if (l32 == 31 && my_member < live) {
-                float sq = 0.0f;
+            for (int i = 0; i < 8; ++i) v8[i] = dpp_halve<0xB1>(acc[i], acc[i + 8], up0);  // quad_perm:[1,0,3,2]
 #pragma unroll
-                for (int a = 0; a < A_MAX; ++a) {
-                    const float av = fminf(fmaxf(acc[a] + b_l[my_member * A_MAX + a], -1.0f), 1.0f);
-                    hact_l[my_member * KS + ((a < 16) ? (16 + a) : 32)] = f2b7(av);
-                    sq = fmaf(av, av, sq);
-                }
-                actsq_total += sq;
+            for (int i = 0; i < 4; ++i) v4[i] = dpp_halve<0x4E>(v8[i], v8[i + 4], up1);    // quad_perm:[2,3,0,1]
+#pragma unroll
+            for (int i = 0; i < 2; ++i) v2[i] = dpp_halve_xor4(v4[i], v4[i + 2], up2);
+            const float a_sum = row_pair_add(dpp_halve<0x128>(v2[0], v2[1], up3));         // row_ror:8
+            const float a_last = reduce32_dpp(acc[A_MAX - 1]);
+            if (tail_lane) {
+                const float av = fminf(fmaxf(((l32 == 31) ? a_last : a_sum) + my_bias, -1.0f), 1.0f);
+                *my_hact = f2b7(av);
+                *my_actf = av;
             }
         }
         if (wave == 0) {
@@ -318,8 +401,23 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
                 const int m = c_row0 + r;
                 a16[r] = b2f7(hact_l[((m < kM) ? m : 0) * KS + 32]);
             }
+            // Σa² of the step, as ONE fma chain in action order per member
+            // (the summation order the fitness has always had), from the
+            // fp32 actions the tail lanes just published. Every lane of the
+            // half-wave runs its member's chain, branch-free and a slice
+            // per tile, so its LDS and fma latencies hide under the
+            // epilogue; only lane 31's copy is used at wrap-up.
+            constexpr int kSqPerTile = (A_MAX + kTilesPerWave - 1) / kTilesPerWave;
+            const float* af = actf_l + my_member * AF;
+            float sq = 0.0f;
 #pragma unroll
             for (int tw = 0; tw < kTilesPerWave; ++tw) {
+                float av_t[kSqPerTile];
+#pragma unroll
+                for (int u = 0; u < kSqPerTile; ++u) {
+                    const int a = tw * kSqPerTile + u;
+                    av_t[u] = (a < A_MAX) ? af[a] : 0.0f;
+                }
                 const int col = (wave * kTilesPerWave + tw) * 16 + c_col;
                 floatx4_t acc = {0.f, 0.f, 0.f, 0.f};
                 const bf16x8_t b0 = *reinterpret_cast<const bf16x8_t*>(ud_l + col * KU + g2_k0);
@@ -348,7 +446,12 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
                 }
                 stat_sum[tw] += ssum;
                 stat_sumsq[tw] += ssq;
+#pragma unroll
+                for (int u = 0; u < kSqPerTile; ++u) {
+                    if (tw * kSqPerTile + u < A_MAX) sq = fmaf(av_t[u], av_t[u], sq);
+                }
             }
+            actsq_total += sq;
         }
         if (!(args.skip_mask & 8)) __syncthreads();
     }
@@ -367,14 +470,14 @@ __global__ __launch_bounds__(64 * kWaves, 1) void rollout_v7_kernel(RolloutV7Arg
 #pragma unroll
         for (int r = 0; r < 4; ++r) wave_fit[wave * 16 + c_row0 + r] = fit_part[r];
     }
-    if (l32 == 31 && my_member < live) actsq_l[my_member] = actsq_total;
+    if (l32 == 31 && my_member < live) actf_l[my_member * AF + A_MAX] = actsq_total;
     __syncthreads();
     if (tid < live) {
         float total = 0.0f;
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) total += wave_fit[w * 16 + tid];
         args.fitness_out[base_member + tid] =
-            total + args.alive_bonus * (float)args.steps - args.act_cost * actsq_l[tid] / (float)A;
+            total + args.alive_bonus * (float)args.steps - args.act_cost * actf_l[tid * AF + A_MAX] / (float)A;
     }
     // per-block stat slice: the four 16-lane groups of a wave share each
     // col (they hold different member rows), so reduce across them with
@@ -720,7 +823,7 @@ static void launch_v7(const RolloutV7Args& args, int n, hipStream_t stream) {
     constexpr int OP = (O_T + 127) / 128 * 128;
     constexpr int kM = 2 * kWaves;
     size_t lds = (size_t)(2 * kM * (OP + 8) + 16 * 72 + 16 * (OP + 8) + OP * 40) * 2 +
-                 (size_t)(kM * A_T + 5 * OP + kWaves * 16 + kM) * 4;
+                 (size_t)(kM * ((A_T + 1 + 3) / 4 * 4) + 5 * OP + kWaves * 16) * 4;
     static bool attr_set7[2] = {false, false};
     const int slot = (kWaves == 8) ? 1 : 0;
     if (!attr_set7[slot]) {
@@ -760,7 +863,13 @@ void rollout_v7(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_
     if (const char* skp = getenv("EVOTORCH_AMD_V7_SKIP")) args.skip_mask = atoi(skp);  // perf probe only
     const char* wenv = getenv("EVOTORCH_AMD_ROLLOUT_V7_WAVES");
     if (wenv && atoi(wenv) == 4) {
+        // 8-member blocks: twice as many stat rows as the caller sized for
+        // 16-member blocks, so they go to a slice of our own and their
+        // (deterministic) sum into the caller's zeroed first row
+        auto part4 = torch::zeros({(int64_t)((n + 7) / 8), 2 * (int64_t)O}, obs_stats_out.options());
+        args.obs_stats_out = part4.data_ptr<float>();
         launch_v7<O_T, A_T, 4>(args, n, stream);
+        obs_stats_out.select(0, 0).add_(part4.sum(0));
     } else {
         launch_v7<O_T, A_T, 8>(args, n, stream);
     }
