@@ -2,10 +2,16 @@
 // through the synthetic vectorized environment, one kernel launch per
 // generation (SURVEY.md §3.4 — the VecGymNE hot loop, collapsed).
 //
+// This file holds the dispatcher `rollout_linear` — the one place that
+// validates, fills RolloutArgs, picks a kernel and sums the obs-stat
+// partials — and v6, the general kernel (any geometry, linear or MLP
+// policy). The Humanoid-geometry kernels live in rollout_v7.hip (linear,
+// MFMA) and rollout_m7.hip (MLP-64); shared helpers in rollout_common.h.
+//
 // Policies: linear (obs -> act) or one-hidden-layer tanh MLP
 // (obs -> H -> act; H=64 is the reference paper's brax-humanoid config).
 //
-// MI355X design (v6): one workgroup rolls out kMembers (default 2)
+// MI355X design (v6): one workgroup rolls out kMembers (2 where they fit)
 // population members for the entire T-step episode with policy weights
 // AND the shared environment matrices resident in LDS — the inner loop
 // never touches global memory. Multi-member blocks exist because one
@@ -22,8 +28,10 @@
 //   * per-thread dots (U, D2): PAIR-INTERLEAVED COLUMN-MAJOR [K/2][O]
 //     bf16x2 — one 4 B read per dot2 at lane-consecutive addresses.
 // Observation-normalization statistics (sum, sumsq) accumulate per-thread
-// in registers and merge with one atomic pass at the end (K11; they
-// become a single RCCL all-reduce across ranks — SURVEY.md §2.8 P5).
+// in registers; at the end every (block, member) writes its own slice
+// with plain stores and the dispatcher sums the slices with one torch
+// reduction — run-to-run deterministic (K11; they become a single RCCL
+// all-reduce across ranks — SURVEY.md §2.8 P5).
 //
 // Environment spec (must match the eager reference in
 // evotorch_amd/neuroevolution/synthetic_env.py::rollout_eager, which
@@ -44,40 +52,11 @@
 
 #include "philox.h"
 #include "reduce.h"
+#include "rollout_common.h"
 
 namespace ea {
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be a ROCm tensor")
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-__device__ __forceinline__ __bf16 f2b(float v) { return (__bf16)v; }
-__device__ __forceinline__ float b2f(__bf16 v) { return (float)v; }
-
-// tanh via the hardware exp unit (~1e-6 rel error, far below the bf16
-// quantization of every operand; libm tanhf is branchy on the hot path)
-// 8-lane group sum on the VALU pipe: after row_shr 1/2/4 the TOP lane of
-// each 8-lane group (glane == 7) holds the group sum (__shfl_down lowers
-// to ds_bpermute_b32 on the LDS pipe — the v7 kernel measured that
-// contention; same fix here).
-template <int kCtrl6>
-__device__ __forceinline__ float dpp_add6(float x) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), kCtrl6, 0xf, 0xf, true);
-    return x + __builtin_bit_cast(float, moved);
-}
-
-__device__ __forceinline__ float group8_sum_dpp(float x) {
-    x = dpp_add6<0x111>(x);  // row_shr:1
-    x = dpp_add6<0x112>(x);  // row_shr:2
-    x = dpp_add6<0x114>(x);  // row_shr:4
-    return x;                // valid in the top lane of each 8-lane group
-}
-
-__device__ __forceinline__ float tanh_fast6(float x) {
-    const float xc = fminf(fmaxf(x, -15.0f), 15.0f);
-    const float e = __expf(2.0f * xc);
-    return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
-}
 
 // runtime member-index -> pointer select WITHOUT a runtime-indexed array
 // (which would demote to scratch memory — common-mistake #20); for
@@ -87,18 +66,52 @@ __device__ __forceinline__ T* sel2(int m, T* p0, T* p1) {
     return m == 0 ? p0 : p1;
 }
 
-struct RolloutArgs {
-    const float* params;      // [n_members][L]
-    const float* env_blob;    // packed fp32 env data (see env_blob())
-    float* fitness_out;       // [n_members]
-    float* obs_stats_out;     // [2][O]  (sum, sumsq) — atomically accumulated
-    int n_members;
-    long member_offset;       // global id of member 0 (rank sharding)
-    int obs_dim, act_dim, rank, steps, hidden;
-    float alive_bonus, act_cost;
-    unsigned long long init_seed;
-    const unsigned long long* seed_ptr;  // device episode seed (hipGraph-safe); overrides init_seed
+// Dynamic-LDS layout of the v6 kernel (byte offsets): the one statement of
+// it, for the kernel's carve-up and the launcher's footprint alike.
+struct V6Layout {
+    int A_PAD, R_PAD;                                       // even, with at least one zero pad element
+    size_t V, U_pair, D2_pair, c, wr, mean, istd, scratch;  // shared environment
+    size_t member0, member_stride;                          // member m's region starts at member0 + m * member_stride
+    size_t W1, b1, W2, b2, hid, obs, obsn, h, act;          // within a member's region
+    size_t bytes;
 };
+
+__host__ __device__ inline V6Layout v6_layout(int O, int A, int R, int H, int members) {
+    V6Layout l;
+    l.A_PAD = (A + 2) & ~1;
+    l.R_PAD = (R + 2) & ~1;
+    const size_t w1_rows = (H > 0) ? H : A;
+    size_t at = 0;
+    const auto take = [&at](size_t n_bytes) {
+        const size_t offset = at;
+        at += n_bytes;
+        return offset;
+    };
+    l.V = take((size_t)R * O * 2);                  // bf16 [R][O]
+    l.U_pair = take((size_t)l.R_PAD / 2 * O * 4);   // bf16x2 [R_PAD/2][O]
+    l.D2_pair = take((size_t)l.A_PAD / 2 * O * 4);  // bf16x2 [A_PAD/2][O]
+    l.c = take((size_t)O * 4);                      // float [O]
+    l.wr = take((size_t)O * 4);                     // float [O]
+    l.mean = take((size_t)O * 4);                   // float [O]
+    l.istd = take((size_t)O * 4);                   // float [O]
+    l.scratch = take(16 * 4);                       // float [16] block-reduction scratch
+    l.member0 = at;
+    at = 0;
+    l.W1 = take(w1_rows * O * 2);                   // bf16, linear: [A][O]; MLP: [H][O]
+    l.b1 = take(w1_rows * 4);                       // float, linear: [A]; MLP: [H]
+    l.W2 = take(H > 0 ? (size_t)A * H * 2 : 0);     // bf16 [A][H], MLP only
+    l.b2 = take(H > 0 ? (size_t)A * 4 : 0);         // float [A], MLP only
+    l.hid = take(H > 0 ? (size_t)H * 2 : 0);        // bf16 [H], MLP only
+    l.obs = take((size_t)O * 2);                    // bf16 [O]
+    l.obsn = take((size_t)O * 2);                   // bf16 [O]
+    l.h = take((size_t)l.R_PAD * 2);                // bf16 [R_PAD]
+    l.act = take((size_t)l.A_PAD * 2);              // bf16 [A_PAD]
+    l.member_stride = at;
+    // 64 B of tail slack the launcher has always requested; kept so the
+    // footprint and the two-member threshold stay where they were
+    l.bytes = l.member0 + (size_t)members * l.member_stride + 64;
+    return l;
+}
 
 // one group-reduced dot output: 8 lanes compute row·vec, lane 0 of the
 // group applies the epilogue selected by `kind`
@@ -112,9 +125,6 @@ struct OutDesc {
     bool valid;
 };
 
-// env_blob layout (fp32): V [R][O] · U_T [R][O] · D2_T [A][O] · c [O] ·
-// wr [O] · mean [O] · std [O]
-
 template <int kGroup, int kMembers>
 __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args) {
     const int O = args.obs_dim, A = args.act_dim, R = args.rank, H = args.hidden;
@@ -122,87 +132,67 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
     const int base_member = blockIdx.x * kMembers;
     if (base_member >= args.n_members) return;
     const int live_members = min(kMembers, args.n_members - base_member);
-    const int A_PAD = (A + 2) & ~1;
-    const int R_PAD = (R + 2) & ~1;
     const long param_len = (H > 0) ? ((long)H * O + H + (long)A * H + A) : ((long)A * O + A);
 
     extern __shared__ unsigned char lds_raw[];
+    const V6Layout lay = v6_layout(O, A, R, H, kMembers);
+    const int A_PAD = lay.A_PAD, R_PAD = lay.R_PAD;
     // ---- shared environment ----
-    __bf16* V_l = reinterpret_cast<__bf16*>(lds_raw);          // [R][O]
-    bf16x2* U_pair = reinterpret_cast<bf16x2*>(V_l + R * O);   // [R_PAD/2][O]
-    bf16x2* D2_pair = U_pair + (R_PAD / 2) * O;                // [A_PAD/2][O]
-    float* c_l = reinterpret_cast<float*>(D2_pair + (A_PAD / 2) * O);  // [O]
-    float* wr_l = c_l + O;                                     // [O]
-    float* mean_l = wr_l + O;                                  // [O]
-    float* istd_l = mean_l + O;                                // [O]
-    float* scratch = istd_l + O;                               // [16]
-    // ---- per-member state ----
-    __bf16* W1_l[kMembers];   // linear: [A][O]; MLP: [H][O]
-    float* b1_l[kMembers];    // linear: [A];    MLP: [H]
-    __bf16* W2_l[kMembers];   // MLP only: [A][H]
-    float* b2_l[kMembers];    // MLP only: [A]
-    __bf16* hid_b[kMembers];  // MLP only: [H]
+    __bf16* V_l = reinterpret_cast<__bf16*>(lds_raw + lay.V);
+    bf16x2* U_pair = reinterpret_cast<bf16x2*>(lds_raw + lay.U_pair);
+    bf16x2* D2_pair = reinterpret_cast<bf16x2*>(lds_raw + lay.D2_pair);
+    float* c_l = reinterpret_cast<float*>(lds_raw + lay.c);
+    float* wr_l = reinterpret_cast<float*>(lds_raw + lay.wr);
+    float* mean_l = reinterpret_cast<float*>(lds_raw + lay.mean);
+    float* istd_l = reinterpret_cast<float*>(lds_raw + lay.istd);
+    float* scratch = reinterpret_cast<float*>(lds_raw + lay.scratch);
+    // ---- per-member state (W2, b2, hid: MLP only) ----
+    __bf16* W1_l[kMembers];
+    float* b1_l[kMembers];
+    __bf16* W2_l[kMembers];
+    float* b2_l[kMembers];
+    __bf16* hid_b[kMembers];
     __bf16* obs_b[kMembers];
     __bf16* obsn_b[kMembers];
     __bf16* h_b[kMembers];
     __bf16* act_b[kMembers];
-    {
-        unsigned char* cursor = reinterpret_cast<unsigned char*>(scratch + 16);
 #pragma unroll
-        for (int m = 0; m < kMembers; ++m) {
-            const int w1_rows = (H > 0) ? H : A;
-            W1_l[m] = reinterpret_cast<__bf16*>(cursor);
-            cursor += (size_t)w1_rows * O * 2;
-            b1_l[m] = reinterpret_cast<float*>(cursor);
-            cursor += (size_t)w1_rows * 4;
-            if (H > 0) {
-                W2_l[m] = reinterpret_cast<__bf16*>(cursor);
-                cursor += (size_t)A * H * 2;
-                b2_l[m] = reinterpret_cast<float*>(cursor);
-                cursor += (size_t)A * 4;
-                hid_b[m] = reinterpret_cast<__bf16*>(cursor);
-                cursor += (size_t)H * 2;
-            } else {
-                W2_l[m] = nullptr;
-                b2_l[m] = nullptr;
-                hid_b[m] = nullptr;
-            }
-            obs_b[m] = reinterpret_cast<__bf16*>(cursor);
-            cursor += (size_t)O * 2;
-            obsn_b[m] = reinterpret_cast<__bf16*>(cursor);
-            cursor += (size_t)O * 2;
-            h_b[m] = reinterpret_cast<__bf16*>(cursor);
-            cursor += (size_t)R_PAD * 2;
-            act_b[m] = reinterpret_cast<__bf16*>(cursor);
-            cursor += (size_t)A_PAD * 2;
-        }
+    for (int m = 0; m < kMembers; ++m) {
+        unsigned char* mine = lds_raw + lay.member0 + m * lay.member_stride;
+        W1_l[m] = reinterpret_cast<__bf16*>(mine + lay.W1);
+        b1_l[m] = reinterpret_cast<float*>(mine + lay.b1);
+        W2_l[m] = reinterpret_cast<__bf16*>(mine + lay.W2);
+        b2_l[m] = reinterpret_cast<float*>(mine + lay.b2);
+        hid_b[m] = reinterpret_cast<__bf16*>(mine + lay.hid);
+        obs_b[m] = reinterpret_cast<__bf16*>(mine + lay.obs);
+        obsn_b[m] = reinterpret_cast<__bf16*>(mine + lay.obsn);
+        h_b[m] = reinterpret_cast<__bf16*>(mine + lay.h);
+        act_b[m] = reinterpret_cast<__bf16*>(mine + lay.act);
     }
 
     // ---- stage shared env ----
     {
-        const float* e = args.env_blob;
-        const int RO = R * O, AO = A * O;
-        for (int i = tid; i < RO; i += blockDim.x) V_l[i] = f2b(e[i]);
+        const EnvBlob env(args.env_blob, O, A, R);
+        for (int i = tid; i < R * O; i += blockDim.x) V_l[i] = f2b(env.V[i]);
         for (int i = tid; i < (R_PAD / 2) * O; i += blockDim.x) {
             const int i2 = i / O, j = i % O;
             bf16x2 v2;
-            v2.x = (2 * i2 < R) ? f2b(e[RO + (2 * i2) * O + j]) : f2b(0.0f);
-            v2.y = (2 * i2 + 1 < R) ? f2b(e[RO + (2 * i2 + 1) * O + j]) : f2b(0.0f);
+            v2.x = (2 * i2 < R) ? f2b(env.U_T[(2 * i2) * O + j]) : f2b(0.0f);
+            v2.y = (2 * i2 + 1 < R) ? f2b(env.U_T[(2 * i2 + 1) * O + j]) : f2b(0.0f);
             U_pair[i2 * O + j] = v2;
         }
         for (int i = tid; i < (A_PAD / 2) * O; i += blockDim.x) {
             const int m2 = i / O, j = i % O;
             bf16x2 v2;
-            v2.x = (2 * m2 < A) ? f2b(e[2 * RO + (2 * m2) * O + j]) : f2b(0.0f);
-            v2.y = (2 * m2 + 1 < A) ? f2b(e[2 * RO + (2 * m2 + 1) * O + j]) : f2b(0.0f);
+            v2.x = (2 * m2 < A) ? f2b(env.D2_T[(2 * m2) * O + j]) : f2b(0.0f);
+            v2.y = (2 * m2 + 1 < A) ? f2b(env.D2_T[(2 * m2 + 1) * O + j]) : f2b(0.0f);
             D2_pair[m2 * O + j] = v2;
         }
-        const float* tail = e + 2 * RO + AO;
         for (int j = tid; j < O; j += blockDim.x) {
-            c_l[j] = tail[j];
-            wr_l[j] = tail[O + j];
-            mean_l[j] = tail[2 * O + j];
-            istd_l[j] = 1.0f / tail[3 * O + j];
+            c_l[j] = env.c[j];
+            wr_l[j] = env.wr[j];
+            mean_l[j] = env.mean[j];
+            istd_l[j] = 1.0f / env.std[j];
         }
     }
     // ---- stage members: weights, pads, initial observations ----
@@ -380,7 +370,7 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
                     if (descs[r].member == m) actsq_part[m] = fmaf(a, a, actsq_part[m]);      \
                 }                                                                             \
             } else if (descs[r].kind == 2) {                                                  \
-                *descs[r].dst = f2b(tanh_fast6(acc[r] + *descs[r].bias));                          \
+                *descs[r].dst = f2b(tanh_fast(acc[r] + *descs[r].bias));                      \
             } else {                                                                          \
                 *descs[r].dst = f2b(acc[r]);                                                  \
             }                                                                                 \
@@ -418,7 +408,7 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
                 dacc = __builtin_amdgcn_fdot2_f32_bf16(
                     D2_pair[p * O + jo], *reinterpret_cast<const bf16x2*>(av + 2 * p), dacc, false);
             }
-            const float o_new = tanh_fast6(uacc + dacc);
+            const float o_new = tanh_fast(uacc + dacc);
 #pragma unroll
             for (int mm = 0; mm < kMembers; ++mm) {
                 if (m == mm) fit_part[mm] = fmaf(wr_l[jo], o_new, fit_part[mm]);
@@ -438,7 +428,7 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
 #undef GROUP_DOTS
 #undef DOT_EPILOGUE
 
-    // ---- wrap-up: per-member fitness reductions + obs-stat atomics ----
+    // ---- wrap-up: per-member fitness reductions + obs-stat slices ----
 #pragma unroll
     for (int m = 0; m < kMembers; ++m) {
         if (m >= live_members) break;
@@ -465,23 +455,32 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
     }
 }
 
+
+constexpr int kV6Threads = 512;
+
 template <int kGroup, int kMembers>
-static void launch_rollout(int n_blocks, int block, size_t lds_bytes, hipStream_t stream, const RolloutArgs& args) {
+static void launch_rollout_v6(const RolloutArgs& args, int n_blocks, size_t lds_bytes, hipStream_t stream) {
     static bool attr_set = false;
     if (!attr_set && lds_bytes > 64 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_linear_kernel<kGroup, kMembers>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        allow_max_dynamic_lds(reinterpret_cast<const void*>(&rollout_linear_kernel<kGroup, kMembers>));
         attr_set = true;
     }
-    hipLaunchKernelGGL((rollout_linear_kernel<kGroup, kMembers>), dim3(n_blocks), dim3(block), lds_bytes, stream, args);
+    hipLaunchKernelGGL((rollout_linear_kernel<kGroup, kMembers>), dim3(n_blocks), dim3(kV6Threads), lds_bytes, stream,
+                       args);
 }
 
-void rollout_v7(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out, torch::Tensor fitness,
-                int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus, double act_cost,
-                int64_t init_seed, int64_t member_offset, const unsigned long long* seed_ptr);  // rollout_v7.hip
-void rollout_m7(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out, torch::Tensor fitness,
-                int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus, double act_cost,
-                int64_t init_seed, int64_t member_offset, const unsigned long long* seed_ptr);  // rollout_v7.hip
+// v6 members per block: two where they fit in LDS, else one. Checks the
+// footprint and the capacities of the kernel's fixed-size tables.
+static int v6_members_per_block(int O, int A, int R, int H) {
+    const int members = (v6_layout(O, A, R, H, 2).bytes > 160 * 1024) ? 1 : 2;
+    const size_t lds_bytes = v6_layout(O, A, R, H, members).bytes;
+    TORCH_CHECK(lds_bytes <= 160 * 1024, "rollout LDS footprint too large: ", lds_bytes, " bytes");
+    // phase-A round capacity: up to 3 rounds of (threads/8) outputs
+    TORCH_CHECK(members * ((H > 0 ? H : A) + R) <= 3 * kV6Threads / 8, "policy too wide for the 3-round phase-A table");
+    TORCH_CHECK(members * A <= kV6Threads / 8, "act_dim too large for the 1-round phase-B table");
+    TORCH_CHECK(O * members <= 2 * kV6Threads, "obs_dim too large for the 2-slot stat accumulators");
+    return members;
+}
 
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
@@ -503,32 +502,11 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
     TORCH_CHECK(O % 2 == 0, "obs_dim must be even (bf16x2 packing)");
     TORCH_CHECK(H % 2 == 0, "policy_hidden must be even (bf16x2 packing)");
     auto fitness = torch::empty({n}, params.options());
-    // v7 (MFMA, 16 members/block) serves the linear flagship geometry;
-    // v6 covers MLP policies and off-geometry envs.
-    if (H == 64 && R == 16 && O == 376 && A == 17 && !getenv("EVOTORCH_AMD_ROLLOUT_V6")) {
-        const char* km_env = getenv("EVOTORCH_AMD_M7_MEMBERS");
-        const int m7_members = (km_env && atoi(km_env) == 4) ? 4 : 2;
-        const int n_pblocks = (n + m7_members - 1) / m7_members;
-        auto stat_partials = torch::zeros({(int64_t)n_pblocks, 2 * (int64_t)O}, params.options());
-        rollout_m7(params, env_blob, stat_partials, fitness, obs_dim, act_dim, rank, steps, alive_bonus, act_cost,
-                   init_seed, member_offset, seed_ptr);
-        obs_stats_out.add_(stat_partials.sum(0));
-        return fitness;
-    }
-    if (H == 0 && R == 16 && O == 376 && A == 17 && !getenv("EVOTORCH_AMD_ROLLOUT_V6")) {
-        const int n_blocks7 = (n + 15) / 16;
-        auto stat_partials = torch::zeros({(int64_t)n_blocks7, 2 * (int64_t)O}, params.options());
-        rollout_v7(params, env_blob, stat_partials, fitness, obs_dim, act_dim, rank, steps, alive_bonus, act_cost,
-                   init_seed, member_offset, seed_ptr);
-        obs_stats_out.add_(stat_partials.sum(0));
-        return fitness;
-    }
 
     RolloutArgs args;
     args.params = params.data_ptr<float>();
     args.env_blob = env_blob.data_ptr<float>();
     args.fitness_out = fitness.data_ptr<float>();
-    args.obs_stats_out = obs_stats_out.data_ptr<float>();
     args.n_members = n;
     args.member_offset = (long)member_offset;
     args.obs_dim = O; args.act_dim = A; args.rank = R; args.hidden = H;
@@ -538,32 +516,29 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
     args.init_seed = (unsigned long long)init_seed;
     args.seed_ptr = seed_ptr;
 
-    const int block = 512;
-    const int A_PAD = (A + 2) & ~1, R_PAD = (R + 2) & ~1;
-    const size_t shared_bytes = ((size_t)R * O + (size_t)R_PAD * O + (size_t)A_PAD * O) * 2 + 4 * (size_t)O * 4 + 16 * 4 + 64;
-    const int w1_rows = (H > 0) ? H : A;
-    size_t member_bytes = ((size_t)w1_rows * O + 2 * (size_t)O + R_PAD + A_PAD) * 2 + (size_t)w1_rows * 4;
-    if (H > 0) member_bytes += (size_t)A * H * 2 + (size_t)A * 4 + (size_t)H * 2;
-
-    int members = 2;
-    if (const char* env = getenv("EVOTORCH_AMD_ROLLOUT_MEMBERS")) members = atoi(env);
-    TORCH_CHECK(members == 1 || members == 2, "EVOTORCH_AMD_ROLLOUT_MEMBERS must be 1 or 2");
-    if (shared_bytes + 2 * member_bytes > 160 * 1024) members = 1;
-    const size_t lds_bytes = shared_bytes + (size_t)members * member_bytes;
-    TORCH_CHECK(lds_bytes <= 160 * 1024, "rollout LDS footprint too large: ", lds_bytes, " bytes");
-    // phase-A round capacity: up to 3 rounds of (threads/8) outputs
-    TORCH_CHECK(members * ((H > 0 ? H : A) + R) <= 3 * block / 8, "policy too wide for the 3-round phase-A table");
-    TORCH_CHECK(members * A <= block / 8, "act_dim too large for the 1-round phase-B table");
-    TORCH_CHECK(O * members <= 2 * block, "obs_dim too large for the 2-slot stat accumulators");
+    // v7 (MFMA, linear) and m7 (MLP-64) serve the Humanoid geometry; v6
+    // covers every other geometry and policy width, and that geometry too
+    // when EVOTORCH_AMD_ROLLOUT_V6 is set. Read on every call: tests change
+    // it within a process.
+    const bool humanoid = R == 16 && O == 376 && A == 17 && !getenv("EVOTORCH_AMD_ROLLOUT_V6");
+    const bool use_v7 = humanoid && H == 0, use_m7 = humanoid && H == 64;
+    const int members = use_v7 ? kV7MembersPerBlock : use_m7 ? kM7MembersPerBlock : v6_members_per_block(O, A, R, H);
+    const int n_blocks = (n + members - 1) / members;
+    // obs-stat partials: one row per block (v7, m7) or per (block, member)
+    // (v6). The shapes fix the order of the torch reduction below.
+    const int64_t stat_rows = (use_v7 || use_m7) ? n_blocks : (int64_t)n_blocks * members;
+    auto stat_partials = torch::zeros({stat_rows, 2 * (int64_t)O}, params.options());
+    args.obs_stats_out = stat_partials.data_ptr<float>();
 
     auto stream = at::cuda::getCurrentCUDAStream();
-    const int n_blocks = (n + members - 1) / members;
-    auto stat_partials = torch::zeros({(int64_t)n_blocks * members, 2 * (int64_t)O}, params.options());
-    args.obs_stats_out = stat_partials.data_ptr<float>();
-    if (members == 2) {
-        launch_rollout<8, 2>(n_blocks, block, lds_bytes, stream, args);
+    if (use_v7) {
+        launch_rollout_v7(args, n, stream);
+    } else if (use_m7) {
+        launch_rollout_m7(args, n, stream);
+    } else if (members == 2) {
+        launch_rollout_v6<8, 2>(args, n_blocks, v6_layout(O, A, R, H, 2).bytes, stream);
     } else {
-        launch_rollout<8, 1>(n_blocks, block, lds_bytes, stream, args);
+        launch_rollout_v6<8, 1>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
     }
     obs_stats_out.add_(stat_partials.sum(0));
     return fitness;

@@ -26,6 +26,7 @@ setup(
                 os.path.join(SRC, "es_kernels.hip"),
                 os.path.join(SRC, "rollout.hip"),
                 os.path.join(SRC, "rollout_v7.hip"),
+                os.path.join(SRC, "rollout_m7.hip"),
                 os.path.join(SRC, "pareto.hip"),
                 os.path.join(SRC, "cma.hip"),
             ],

@@ -34,8 +34,7 @@ def C():
 
 @pytest.fixture(autouse=True)
 def _default_kernel(monkeypatch):
-    for name in ("EVOTORCH_AMD_ROLLOUT_V7_WAVES", "EVOTORCH_AMD_V7_SKIP", "EVOTORCH_AMD_ROLLOUT_V6"):
-        monkeypatch.delenv(name, raising=False)
+    monkeypatch.delenv("EVOTORCH_AMD_ROLLOUT_V6", raising=False)
 
 
 def _spec(steps):
@@ -116,11 +115,6 @@ class TestBlocks:
         _, efit = _check(C, "plain", n, 8)
         if n > 1:
             assert efit.std() > 10 * FIT_TOL["atol"]  # the members are told apart
-
-    @pytest.mark.parametrize("n", [1, 8, 9])
-    def test_partial_and_multiple_blocks_4_waves(self, C, monkeypatch, n):
-        monkeypatch.setenv("EVOTORCH_AMD_ROLLOUT_V7_WAVES", "4")
-        _check(C, "plain", n, 8)
 
 
 @requires_gpu
