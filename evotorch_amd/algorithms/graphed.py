@@ -76,10 +76,10 @@ class GraphedSearch:
 
         from .. import ops
         from ..core import SolutionBatch
-        from ..ops.dispatch import _seed_from_generator
+        from ..ops import seed_from_generator
 
         self._C = ops.hip_required()
-        seed0 = _seed_from_generator(problem.generator, problem.device)
+        seed0 = seed_from_generator(problem.generator, problem.device)
         self._seed_buf = torch.tensor([seed0], dtype=torch.int64, device=problem.device)
         if searcher._population is None:
             searcher._population = SolutionBatch(problem, popsize=searcher._popsize, device=dist.device, empty=True)

@@ -94,10 +94,11 @@ class MAPElites(SearchAlgorithm, SinglePopulationAlgorithmMixin, ExtendedPopulat
         if features.is_cuda:
             # K9 HIP kernel: streamed best-in-box argmax, O(C + N) memory
             # (the eager broadcast below materializes a (C, N) matrix)
-            from ..ops.dispatch import _allow_eager_on_gpu, hip_required
+            from ..ops import hip_for
 
-            if not _allow_eager_on_gpu():
-                best_idx, any_valid = hip_required().mapelites_assign(self._feature_grid, features, utils)
+            mod = hip_for(features)
+            if mod is not None:
+                best_idx, any_valid = mod.mapelites_assign(self._feature_grid, features, utils)
                 return best_idx, any_valid
         f = features.unsqueeze(0)  # (1, N, F)
         inside = ((f >= lo) & (f <= hi)).all(dim=-1)  # (C, N)

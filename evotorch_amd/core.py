@@ -1038,10 +1038,10 @@ class Problem(TensorMakerMixin, Serializable):
         for a deterministic fitness function — is IDENTICAL for any world
         size that divides the popsize (SURVEY.md §7 "RNG discipline"). Rank
         seeds need not match; rank 0's generator decides."""
-        from .ops.dispatch import _seed_from_generator
+        from .ops import seed_from_generator
 
         self._comm = comm
-        base = _seed_from_generator(self._generator, self._device)
+        base = seed_from_generator(self._generator, self._device)
         t = torch.tensor([base], dtype=torch.int64)
         comm.broadcast_(t, src=0)
         self._spmd_seed_base = int(t.item()) & 0x7FFFFFFFFFFFFFFF
@@ -1050,17 +1050,17 @@ class Problem(TensorMakerMixin, Serializable):
 
     def _next_spmd_seed(self) -> int:
         """Next seed of the shared chain (all ranks advance in lockstep)."""
-        from .ops.dispatch import _splitmix64
+        from .ops.dispatch import splitmix64
 
         self._spmd_gen_counter += 1
-        return _splitmix64(self._spmd_seed_base ^ (self._spmd_gen_counter * 0x9E3779B97F4A7C15))
+        return splitmix64(self._spmd_seed_base ^ (self._spmd_gen_counter * 0x9E3779B97F4A7C15))
 
     def _peek_spmd_seed(self, ahead: int = 1) -> int:
         """Look ahead in the shared seed chain without advancing it (the
         side-stream noise pre-generation needs next generation's seed)."""
-        from .ops.dispatch import _splitmix64
+        from .ops.dispatch import splitmix64
 
-        return _splitmix64(self._spmd_seed_base ^ ((self._spmd_gen_counter + ahead) * 0x9E3779B97F4A7C15))
+        return splitmix64(self._spmd_seed_base ^ ((self._spmd_gen_counter + ahead) * 0x9E3779B97F4A7C15))
 
     # -- side-stream noise pre-generation (SURVEY.md §2.8 P2 overlap) --------
     #
@@ -1622,7 +1622,7 @@ class Problem(TensorMakerMixin, Serializable):
         if not hasattr(distribution, "fill_counter_addressed"):
             raise ValueError(f"{type(distribution).__name__} does not support streamed gradients")
         elite_mode = "parenthood_ratio" in getattr(distribution, "parameters", {})
-        from .ops.dispatch import _seed_from_generator
+        from .ops import seed_from_generator
         from .utils import ranking as ranking_mod
 
         world = comm.world_size if comm is not None else 1
@@ -1635,7 +1635,7 @@ class Problem(TensorMakerMixin, Serializable):
         my_dir0 = my_rank * directions
         # stream-per-row philox addressing: any chunk boundary is exact
         chunk_rows = min(chunk_rows, directions)
-        seed = self._next_spmd_seed() if comm is not None else _seed_from_generator(self._generator, self._device)
+        seed = self._next_spmd_seed() if comm is not None else seed_from_generator(self._generator, self._device)
 
         fits = torch.empty(local_popsize, dtype=self._eval_dtype, device=self._device)
 

@@ -86,19 +86,19 @@ class SyntheticRolloutProblem(Problem):
         if self._device.type != "cuda":
             return
         if getattr(self, "_graph_seed_buf", None) is None:
-            from ..ops.dispatch import _seed_from_generator
+            from ..ops import seed_from_generator
 
-            seed0 = _seed_from_generator(self._generator, self._device)
+            seed0 = seed_from_generator(self._generator, self._device)
             self._graph_seed_buf = torch.tensor([seed0], dtype=torch.int64, device=self._device)
 
     def _evaluate_batch(self, batch: SolutionBatch):
         values = batch.access_values(keep_evals=True)
         n = len(batch)
         spec = self._spec
-        from ..ops.dispatch import _seed_from_generator
+        from ..ops import seed_from_generator
 
         seed_buf = getattr(self, "_graph_seed_buf", None)
-        init_seed = 0 if seed_buf is not None else _seed_from_generator(self._generator, self._device) & 0x7FFFFFFF
+        init_seed = 0 if seed_buf is not None else seed_from_generator(self._generator, self._device) & 0x7FFFFFFF
         member_offset = 0
         comm = self._comm
         if comm is not None and comm.world_size > 1:

@@ -364,9 +364,9 @@ class VecEnvNE(NEProblem):
         policy = self._policy
         params = batch.access_values(keep_evals=True).to(device, torch.float32)
 
-        from ..ops.dispatch import _seed_from_generator
+        from ..ops import seed_from_generator
 
-        episode_seed = _seed_from_generator(self._generator, self._device) & 0x7FFFFFFF
+        episode_seed = seed_from_generator(self._generator, self._device) & 0x7FFFFFFF
         max_steps = self._max_num_steps or getattr(env.spec, "episode_length", None) or 1000
 
         if self._use_hip_graph and device.type == "cuda" and not (self._obs_norm_enabled and not self._obs_norm.has_data):

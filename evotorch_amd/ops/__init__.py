@@ -9,14 +9,17 @@ from .dispatch import (
     cma_update_c_,
     clipup_step_,
     domination_counts,
+    eager_on_gpu,
     es_gradients,
     fused_adam_step_,
     hip_available,
+    hip_for,
     hip_required,
     load_hip,
     pareto_ranks,
     potrf_tile_,
     sample_gaussian,
+    seed_from_generator,
     snes_gradients,
 )
 
@@ -24,12 +27,15 @@ __all__ = [
     "affine_from_noise",
     "cma_update_c_",
     "clipup_step_",
+    "eager_on_gpu",
     "es_gradients",
     "fused_adam_step_",
     "hip_available",
+    "hip_for",
     "hip_required",
     "load_hip",
     "sample_gaussian",
+    "seed_from_generator",
     "snes_gradients",
     "pareto_ranks",
     "potrf_tile_",

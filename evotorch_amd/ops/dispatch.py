@@ -9,12 +9,21 @@ Every hot op of the framework goes through this module. The contract:
   machine that has a GPU, we raise loudly instead of silently falling back
   (the eager path would hide a broken native build).
 
-Kernel inventory: K1 sample_gaussian, K2 ranking utilities
-(torch.sort based — the sort itself is rocPRIM-backed via torch), K3/K4
-es_gradients + fused update, K10 batched policy forward (in
-evotorch_amd.models), K11 running-norm update.
+Kernel inventory (docs/kernels.md): K1 sample_gaussian / affine_from_noise,
+K2 fused_rank (routed from utils/ranking.py), K3 es_gradients /
+snes_gradients, K4 clipup_step / adam_step, K5 cma_update_c, K5b potrf_tile,
+K7 pareto_ranks / domination_counts, K9 mapelites_assign (routed from
+algorithms/mapelites.py), K10+K11 rollout_linear (called from
+neuroevolution/synthetic.py).
+
+The launchers check every operand (ops/hip/check.h): dense, on the primary
+tensor's device, of its dtype and of exactly the length the kernel reads.
+The casts below hand them what they expect; `hip_for` is the one routing
+decision.
 """
 
+import contextlib
+import functools
 import os
 from typing import Optional, Tuple
 
@@ -22,9 +31,12 @@ import torch
 
 __all__ = [
     "affine_from_noise",
+    "eager_on_gpu",
     "hip_available",
+    "hip_for",
     "hip_required",
     "load_hip",
+    "seed_from_generator",
     "sample_gaussian",
     "es_gradients",
     "snes_gradients",
@@ -35,24 +47,17 @@ __all__ = [
     "cma_update_c_",
 ]
 
-_hip_module = None
-_hip_load_attempted = False
 
-
+@functools.lru_cache(maxsize=None)
 def load_hip():
     """Load the in-tree HIP extension (returns None on failure, caching the
     outcome)."""
-    global _hip_module, _hip_load_attempted
-    if _hip_load_attempted:
-        return _hip_module
-    _hip_load_attempted = True
     try:
         import evotorch_amd._C as _C  # built in-tree by setup_hip.py / __graft_entry__.build()
 
-        _hip_module = _C
+        return _C
     except ImportError:
-        _hip_module = None
-    return _hip_module
+        return None
 
 
 def hip_available() -> bool:
@@ -72,15 +77,42 @@ def hip_required():
     return mod
 
 
-def _allow_eager_on_gpu() -> bool:
-    # escape hatch for debugging only
-    return os.environ.get("EVOTORCH_AMD_ALLOW_EAGER_GPU", "0") == "1"
+_EAGER_ENV = "EVOTORCH_AMD_ALLOW_EAGER_GPU"  # escape hatch for debugging and reference runs only
+
+
+def hip_for(t: torch.Tensor):
+    """The extension when `t` is a ROCm tensor that must take the HIP path
+    (loud error if it is not built), else None: CPU tensors, and ROCm
+    tensors while the eager escape hatch is on, run the eager reference."""
+    if t.device.type == "cuda" and os.environ.get(_EAGER_ENV, "0") != "1":
+        return hip_required()
+    return None
+
+
+@contextlib.contextmanager
+def eager_on_gpu():
+    """Route ROCm tensors to the eager references inside the block; the
+    environment is left exactly as it was found."""
+    previous = os.environ.get(_EAGER_ENV)
+    os.environ[_EAGER_ENV] = "1"
+    try:
+        yield
+    finally:
+        if previous is None:
+            del os.environ[_EAGER_ENV]
+        else:
+            os.environ[_EAGER_ENV] = previous
+
+
+def _dense(like: torch.Tensor, *operands: torch.Tensor):
+    # what the launchers accept beside `like`: its dtype, no strides
+    return [t.to(like.dtype).contiguous() for t in operands]
 
 
 _SPLITMIX_INC = 0x9E3779B97F4A7C15
 _seed_fallback_counter = [0x1234ABCD]
 
-def _splitmix64(x: int) -> int:
+def splitmix64(x: int) -> int:
     x = (x + _SPLITMIX_INC) & 0xFFFFFFFFFFFFFFFF
     z = x
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
@@ -88,7 +120,7 @@ def _splitmix64(x: int) -> int:
     return (z ^ (z >> 31)) & 0x7FFFFFFFFFFFFFFF
 
 
-def _seed_from_generator(generator: Optional[torch.Generator], device: torch.device) -> int:
+def seed_from_generator(generator: Optional[torch.Generator], device: torch.device) -> int:
     """Derive a fresh 63-bit seed deterministically from the generator's OWN
     state — no global bookkeeping, no device sync.
 
@@ -109,10 +141,10 @@ def _seed_from_generator(generator: Optional[torch.Generator], device: torch.dev
             off = int(generator.get_offset())
             generator.set_offset(off + 4)
             mixed = (int(generator.initial_seed()) ^ ((off + 1) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
-            return _splitmix64(mixed)
+            return splitmix64(mixed)
         return int(torch.randint(0, 2**62, (1,), generator=generator).item())
     _seed_fallback_counter[0] += 1
-    return _splitmix64(_seed_fallback_counter[0])
+    return splitmix64(_seed_fallback_counter[0])
 
 
 # ============================================================================
@@ -145,31 +177,18 @@ def sample_gaussian(
     n = out.shape[0]
     if symmetric and n % 2 != 0:
         raise ValueError("symmetric sampling requires even popsize")
+    mod = hip_for(out)
+    if mod is not None:
+        if seed is None:  # a fresh seed from the generator; row_offset addresses seeded streams only
+            seed, row_offset = seed_from_generator(generator, out.device), 0
+        mod.sample_gaussian(out, *_dense(out, mu, sigma), bool(symmetric), int(seed), int(row_offset))
+        return out
     if seed is not None:
-        if out.device.type == "cuda" and not _allow_eager_on_gpu():
-            mod = hip_required()
-            mod.sample_gaussian(out, mu.to(out.dtype), sigma.to(out.dtype), bool(symmetric), int(seed), int(row_offset))
-            return out
         # philox-exact eager reference (matches the kernel bit-for-bit in fp32)
         from ..neuroevolution.philox_ref import philox_normals_2d
 
-        rows = n // 2 if symmetric else n
-        length = out.shape[1]
-        z = philox_normals_2d(int(seed), int(row_offset), rows, length).to(device=out.device)
-        mu32 = mu.to(torch.float32)
-        sigma32 = sigma.to(torch.float32)
-        plus = (mu32 + sigma32 * z).to(out.dtype)
-        if symmetric:
-            out[:rows] = plus
-            out[rows:] = (2.0 * mu32 - plus.to(torch.float32)).to(out.dtype)
-        else:
-            out.copy_(plus)
-        return out
-    if out.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
-        drawn = _seed_from_generator(generator, out.device)
-        mod.sample_gaussian(out, mu.to(out.dtype), sigma.to(out.dtype), bool(symmetric), drawn, 0)
-        return out
+        z = philox_normals_2d(int(seed), int(row_offset), n // 2 if symmetric else n, out.shape[1])
+        return _affine_eager(out, z.to(device=out.device), mu, sigma, symmetric)
     # eager reference
     if symmetric:
         half = out[: n // 2]
@@ -194,10 +213,14 @@ def affine_from_noise(
     counter-addressed on a side stream, hidden behind evaluation and the
     gradient all-reduce). Bitwise-identical to `sample_gaussian` with the
     same seed/row_offset: both compute fmaf(sigma, z, mu) in fp32."""
-    if out.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
-        mod.affine_from_noise(out, z, mu.to(out.dtype), sigma.to(out.dtype), bool(symmetric))
+    mod = hip_for(out)
+    if mod is not None:
+        mod.affine_from_noise(out, z, *_dense(out, mu, sigma), bool(symmetric))
         return out
+    return _affine_eager(out, z, mu, sigma, symmetric)
+
+
+def _affine_eager(out, z, mu, sigma, symmetric):
     n = out.shape[0]
     rows = n // 2 if symmetric else n
     mu32 = mu.to(torch.float32)
@@ -236,24 +259,18 @@ def es_gradients(
         mu_grad[l]    = Σ_d (w⁺_d − w⁻_d)/2 · noise_dl
         sigma_grad[l] = Σ_d (w⁺_d + w⁻_d)/2 · (noise_dl² − σ_l²)/σ_l
     """
-    if samples.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
-        return mod.es_gradients(samples, mu.to(samples.dtype), sigma.to(samples.dtype), weights.to(samples.dtype), bool(symmetric))
+    mod = hip_for(samples)
+    if mod is not None:
+        return mod.es_gradients(samples, *_dense(samples, mu, sigma, weights), bool(symmetric))
+    w_mu = w_sigma = weights.to(torch.float32)
     if symmetric:
-        n = samples.shape[0]
-        d = n // 2
-        noises = samples[:d].to(torch.float32) - mu.to(torch.float32)
-        w_plus = weights[:d].to(torch.float32)
-        w_minus = weights[d:].to(torch.float32)
-        mu_grad = ((w_plus - w_minus) / 2.0) @ noises
-        sigma32 = sigma.to(torch.float32)
-        sigma_grad = ((w_plus + w_minus) / 2.0) @ ((noises**2 - sigma32**2) / sigma32)
-    else:
-        noises = samples.to(torch.float32) - mu.to(torch.float32)
-        w = weights.to(torch.float32)
-        mu_grad = w @ noises
-        sigma32 = sigma.to(torch.float32)
-        sigma_grad = w @ ((noises**2 - sigma32**2) / sigma32)
+        d = samples.shape[0] // 2
+        samples, w_plus, w_minus = samples[:d], w_mu[:d], w_mu[d:]
+        w_mu, w_sigma = (w_plus - w_minus) / 2.0, (w_plus + w_minus) / 2.0
+    noises = samples.to(torch.float32) - mu.to(torch.float32)
+    sigma32 = sigma.to(torch.float32)
+    mu_grad = w_mu @ noises
+    sigma_grad = w_sigma @ ((noises**2 - sigma32**2) / sigma32)
     return mu_grad.to(samples.dtype), sigma_grad.to(samples.dtype)
 
 
@@ -267,9 +284,9 @@ def snes_gradients(
         mu_grad[l]    = Σ_i w_i · (x_il − μ_l)
         sigma_grad[l] = Σ_i w_i · (z_il² − 1),  z = (x − μ)/σ
     """
-    if samples.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
-        return mod.snes_gradients(samples, mu.to(samples.dtype), sigma.to(samples.dtype), weights.to(samples.dtype))
+    mod = hip_for(samples)
+    if mod is not None:
+        return mod.snes_gradients(samples, *_dense(samples, mu, sigma, weights))
     noises = samples.to(torch.float32) - mu.to(torch.float32)
     raw = noises / sigma.to(torch.float32)
     w = weights.to(torch.float32)
@@ -295,9 +312,9 @@ def clipup_step_(
     optimizers.py:231-357). Normalizes grad to unit L2, takes a step of
     `step_size`, adds momentum-scaled velocity, clips the velocity norm to
     `max_speed`. Returns the updated velocity (= the ascent step)."""
-    if velocity.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
-        mod.clipup_step(velocity, grad, float(step_size), float(max_speed), float(momentum))
+    mod = hip_for(velocity)
+    if mod is not None:
+        mod.clipup_step(velocity, *_dense(velocity, grad), float(step_size), float(max_speed), float(momentum))
         return velocity
     g32 = grad.to(torch.float32)
     gnorm = torch.linalg.vector_norm(g32)
@@ -324,9 +341,9 @@ def fused_adam_step_(
 ) -> torch.Tensor:
     """In-place Adam *ascent* step: updates moments m, v and writes the
     additive step into `param_step_out`."""
-    if grad.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
-        mod.adam_step(param_step_out, grad, m, v, int(step_count), float(stepsize), float(beta1), float(beta2), float(epsilon))
+    mod = hip_for(grad)
+    if mod is not None:
+        mod.adam_step(param_step_out, *_dense(param_step_out, grad), m, v, int(step_count), float(stepsize), float(beta1), float(beta2), float(epsilon))
         return param_step_out
     g32 = grad.to(torch.float32)
     m32 = m.to(torch.float32) * beta1 + (1.0 - beta1) * g32
@@ -347,8 +364,9 @@ def fused_adam_step_(
 def domination_counts(utils: torch.Tensor) -> torch.Tensor:
     """Per solution: how many others dominate it. `utils` is (N, M) with
     higher-is-better columns."""
-    if utils.device.type == "cuda" and not _allow_eager_on_gpu():
-        return hip_required().domination_counts(utils).to(torch.int64)
+    mod = hip_for(utils)
+    if mod is not None:
+        return mod.domination_counts(utils).to(torch.int64)
     a = utils.unsqueeze(1)
     b = utils.unsqueeze(0)
     dom = (a >= b).all(dim=-1) & (a > b).any(dim=-1)
@@ -361,8 +379,9 @@ def pareto_ranks(utils: torch.Tensor, min_assigned: Optional[int] = None) -> tor
     `min_assigned`, peeling stops once that many solutions hold final
     ranks (take_best(n) only needs the fronts crossing n); the rest get a
     shared beyond-last rank."""
-    if utils.device.type == "cuda" and not _allow_eager_on_gpu():
-        return hip_required().pareto_ranks(utils, int(min_assigned or 0))
+    mod = hip_for(utils)
+    if mod is not None:
+        return mod.pareto_ranks(utils, int(min_assigned or 0))
     from ..core import _compute_pareto_ranks_eager
 
     ranks, _ = _compute_pareto_ranks_eager(utils, crowdsort=False, min_assigned=min_assigned)
@@ -394,10 +413,9 @@ def cma_update_c_(
     eager reference is the reference-parity torch chain (cmaes.py:547-553)
     plus explicit symmetrization."""
     wsum = w_adj.sum().to(torch.float32)
-    if C.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
-        mod.cma_update_c(C, y.contiguous().to(torch.float32), w_adj.to(torch.float32), p_c.to(torch.float32),
-                         hs_f.reshape(1).to(torch.float32), wsum.reshape(1), float(c1), float(cmu), float(cc))
+    mod = hip_for(C)
+    if mod is not None:
+        mod.cma_update_c(C, *_dense(C, y, w_adj, p_c, hs_f.reshape(1), wsum.reshape(1)), float(c1), float(cmu), float(cc))
         return C
     delta_hs = (1.0 - hs_f) * cc * (2.0 - cc)
     scale = 1.0 + c1 * delta_hs - c1 - cmu * wsum
@@ -424,8 +442,8 @@ def potrf_tile_(A: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.T
     callers must not rely on the upper half either way)."""
     if A.ndim != 2 or A.shape[0] != A.shape[1]:
         raise ValueError(f"expected a square panel, got {tuple(A.shape)}")
-    if A.device.type == "cuda" and not _allow_eager_on_gpu():
-        mod = hip_required()
+    mod = hip_for(A)
+    if mod is not None:
         if info is None:
             info = torch.zeros(1, dtype=torch.int32, device=A.device)
         mod.potrf_tile(A, info)

@@ -19,9 +19,9 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-namespace ea {
+#include "check.h"
 
-#define CHECK_GPU_C(x) TORCH_CHECK(x.is_cuda(), #x " must be a ROCm tensor")
+namespace ea {
 
 constexpr int kTile = 64;
 constexpr int kChunkK = 32;  // Y rows staged per LDS round
@@ -190,19 +190,20 @@ __global__ __launch_bounds__(256) void potrf_panel_kernel(float* __restrict__ A,
 }
 
 void potrf_tile(torch::Tensor A, torch::Tensor info) {
-    CHECK_GPU_C(A);
+    // A may be a strided view (a diagonal block of a larger matrix), so it
+    // is not a check_primary operand: only its rows must be dense
+    TORCH_CHECK(A.is_cuda(), "A must be a ROCm tensor, got ", A.device());
     TORCH_CHECK(A.dim() == 2 && A.size(0) == A.size(1), "A must be square");
     TORCH_CHECK(A.size(0) <= kPotrfMax, "panel larger than ", kPotrfMax);
     TORCH_CHECK(A.stride(1) == 1, "A rows must be contiguous");
     TORCH_CHECK(A.scalar_type() == at::ScalarType::Float, "A must be fp32");
-    TORCH_CHECK(info.is_cuda() && info.scalar_type() == at::ScalarType::Int && info.numel() >= 1,
-                "info must be a device int32 scalar");
+    check_same_device(info, "info", A);
+    TORCH_CHECK(info.scalar_type() == at::ScalarType::Int && info.numel() >= 1, "info must be a device int32 scalar");
     const int n = (int)A.size(0);
     const size_t lds = (size_t)(kPotrfMax * kPotrfPad + kPotrfMax * kPotrfPPad) * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_panel_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        allow_max_dynamic_lds(reinterpret_cast<const void*>(&potrf_panel_kernel));
         attr_set = true;
     }
     auto stream = at::cuda::getCurrentCUDAStream();
@@ -212,13 +213,17 @@ void potrf_tile(torch::Tensor A, torch::Tensor info) {
 
 void cma_update_c(torch::Tensor C, torch::Tensor Y, torch::Tensor w, torch::Tensor pc, torch::Tensor hs_f,
                   torch::Tensor wsum, double c1, double cmu, double cc) {
-    CHECK_GPU_C(C);
-    TORCH_CHECK(C.is_contiguous() && C.dim() == 2 && C.size(0) == C.size(1), "C must be contiguous square");
+    check_primary(C, "C", 2);
+    TORCH_CHECK(C.size(0) == C.size(1), "C must be square, got ", C.sizes());
     TORCH_CHECK(C.scalar_type() == at::ScalarType::Float, "C must be fp32");
-    TORCH_CHECK(Y.is_contiguous() && Y.scalar_type() == at::ScalarType::Float, "Y must be contiguous fp32");
     const int d = (int)C.size(0);
+    TORCH_CHECK(Y.dim() == 2 && Y.size(1) == d, "Y must be (lam, ", d, "), got ", Y.sizes());
     const int lam = (int)Y.size(0);
-    TORCH_CHECK(Y.size(1) == d && w.numel() == lam && pc.numel() == d, "shape mismatch");
+    check_operand(Y, "Y", C, (int64_t)lam * d);
+    check_operand(w, "w", C, lam);
+    check_operand(pc, "pc", C, d);
+    check_operand(hs_f, "hs_f", C, 1);
+    check_operand(wsum, "wsum", C, 1);
     const int ntiles = (d + kTile - 1) / kTile;
     const int nblocks = ntiles * (ntiles + 1) / 2;
     auto stream = at::cuda::getCurrentCUDAStream();

@@ -19,15 +19,16 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-#include <algorithm>
-
+#include "check.h"
 #include "philox.h"
 #include "reduce.h"
 
-#define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be a ROCm tensor")
-#define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
-
 namespace ea {
+
+// Run `...` with T bound to the tensor's element type (fp64, fp32, fp16, bf16).
+#define DISPATCH_FLOAT_T(tensor, name, ...)                                                                    \
+    AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half, (tensor).scalar_type(), name, \
+                                    [&] { using T = scalar_t; __VA_ARGS__ })
 
 // ---------------------------------------------------------------------------
 // K1: sampling
@@ -125,42 +126,41 @@ __global__ void sample_gaussian_f32x4_kernel(float4* __restrict__ out, const flo
     }
 }
 
-void sample_gaussian_impl(torch::Tensor out, torch::Tensor mu, torch::Tensor sigma, bool symmetric, int64_t seed,
-                          const unsigned long long* seed_ptr, int64_t row_offset = 0) {
+// Operands of the sampling-shaped entry points: `out` is N x L, mu and sigma
+// are dense L-vectors of its dtype. Returns the rows a launch generates
+// (N, or N/2 mirrored directions when symmetric).
+static int64_t check_sampling_operands(const torch::Tensor& out, const torch::Tensor& mu, const torch::Tensor& sigma,
+                                       bool symmetric) {
+    check_primary(out, "out", 2);
+    check_operand(mu, "mu", out, out.size(1));
+    check_operand(sigma, "sigma", out, out.size(1));
+    TORCH_CHECK(!symmetric || out.size(0) % 2 == 0, "symmetric sampling needs even popsize, got ", out.size(0));
+    return symmetric ? out.size(0) / 2 : out.size(0);
+}
+
+static void sample_gaussian_impl(torch::Tensor out, torch::Tensor mu, torch::Tensor sigma, bool symmetric, int64_t seed,
+                                 const unsigned long long* seed_ptr, int64_t row_offset = 0) {
     TORCH_CHECK(row_offset >= 0, "row_offset must be non-negative");
-    CHECK_GPU(out); CHECK_CONTIG(out); CHECK_GPU(mu); CHECK_GPU(sigma);
-    const int64_t n = out.size(0), length = out.size(1);
-    TORCH_CHECK(!symmetric || n % 2 == 0, "symmetric sampling needs even popsize");
-    const int64_t rows = symmetric ? n / 2 : n;
+    const int64_t rows = check_sampling_operands(out, mu, sigma, symmetric);
+    const int64_t length = out.size(1);
     const int threads = 256;
-    const int64_t len4 = (length + 3) / 4;
-    const int64_t total4 = rows * len4;
     // 2048 blocks (8/CU) saturate: deeper grids measured identical (the
     // SQ_WAIT:BUSY ~12:1 is philox->Box-Muller dependency latency plus the
     // write pipe, not occupancy starvation)
-    const int blocks = (int)std::min<int64_t>((total4 + threads - 1) / threads, 256 * 8);
+    const int blocks = grid_for(rows * ((length + 3) / 4), threads, 256 * 8);
     auto stream = at::cuda::getCurrentCUDAStream();
-    if (out.scalar_type() == at::ScalarType::Float && length % 4 == 0 && mu.is_contiguous() && sigma.is_contiguous()) {
-        if (symmetric) {
-            hipLaunchKernelGGL((sample_gaussian_f32x4_kernel<true>), dim3(blocks), dim3(threads), 0, stream,
-                               reinterpret_cast<float4*>(out.data_ptr<float>()), reinterpret_cast<const float4*>(mu.data_ptr<float>()),
-                               reinterpret_cast<const float4*>(sigma.data_ptr<float>()), rows, length / 4, (uint64_t)seed, seed_ptr, row_offset);
-        } else {
-            hipLaunchKernelGGL((sample_gaussian_f32x4_kernel<false>), dim3(blocks), dim3(threads), 0, stream,
-                               reinterpret_cast<float4*>(out.data_ptr<float>()), reinterpret_cast<const float4*>(mu.data_ptr<float>()),
-                               reinterpret_cast<const float4*>(sigma.data_ptr<float>()), rows, length / 4, (uint64_t)seed, seed_ptr, row_offset);
-        }
+    if (out.scalar_type() == at::ScalarType::Float && length % 4 == 0) {
+        auto kernel = symmetric ? sample_gaussian_f32x4_kernel<true> : sample_gaussian_f32x4_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream, reinterpret_cast<float4*>(out.data_ptr<float>()),
+                           reinterpret_cast<const float4*>(mu.data_ptr<float>()),
+                           reinterpret_cast<const float4*>(sigma.data_ptr<float>()), rows, length / 4, (uint64_t)seed,
+                           seed_ptr, row_offset);
         return;
     }
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half, out.scalar_type(), "sample_gaussian", [&] {
-        using T = scalar_t;
-        if (symmetric) {
-            hipLaunchKernelGGL((sample_gaussian_kernel<T, true>), dim3(blocks), dim3(threads), 0, stream,
-                               out.data_ptr<T>(), mu.data_ptr<T>(), sigma.data_ptr<T>(), rows, length, (uint64_t)seed, seed_ptr, row_offset);
-        } else {
-            hipLaunchKernelGGL((sample_gaussian_kernel<T, false>), dim3(blocks), dim3(threads), 0, stream,
-                               out.data_ptr<T>(), mu.data_ptr<T>(), sigma.data_ptr<T>(), rows, length, (uint64_t)seed, seed_ptr, row_offset);
-        }
+    DISPATCH_FLOAT_T(out, "sample_gaussian", {
+        auto kernel = symmetric ? sample_gaussian_kernel<T, true> : sample_gaussian_kernel<T, false>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream, out.data_ptr<T>(), mu.data_ptr<T>(),
+                           sigma.data_ptr<T>(), rows, length, (uint64_t)seed, seed_ptr, row_offset);
     });
 }
 
@@ -169,28 +169,21 @@ void sample_gaussian(torch::Tensor out, torch::Tensor mu, torch::Tensor sigma, b
     sample_gaussian_impl(out, mu, sigma, symmetric, seed, nullptr, row_offset);
 }
 
+// Advance a device seed chain by one splitmix64 step (standalone entry for
+// graph-safe consumers like the rollout kernels: bump, then launch with
+// seed_buf — replays draw fresh episode seeds).
+void bump_seed(torch::Tensor seed_buf) {
+    hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(1), 0, at::cuda::getCurrentCUDAStream(),
+                       device_i64_scalar(seed_buf, "seed_buf"));
+}
+
 // Graph-safe variant: the seed lives in `seed_buf` (int64 tensor of 1
 // element) and is advanced ON DEVICE after sampling, so hipGraph replays
 // draw fresh populations.
 void sample_gaussian_graphsafe(torch::Tensor out, torch::Tensor mu, torch::Tensor sigma, bool symmetric,
                                torch::Tensor seed_buf) {
-    TORCH_CHECK(seed_buf.is_cuda() && seed_buf.scalar_type() == at::ScalarType::Long && seed_buf.numel() >= 1,
-                "seed_buf must be a cuda int64 tensor");
-    auto* ptr = reinterpret_cast<unsigned long long*>(seed_buf.data_ptr<int64_t>());
-    sample_gaussian_impl(out, mu, sigma, symmetric, 0, ptr);
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(1), 0, stream, ptr);
-}
-
-// Advance a device seed chain by one splitmix64 step (standalone entry for
-// graph-safe consumers like the rollout kernels: bump, then launch with
-// seed_buf — replays draw fresh episode seeds).
-void bump_seed(torch::Tensor seed_buf) {
-    TORCH_CHECK(seed_buf.is_cuda() && seed_buf.scalar_type() == at::ScalarType::Long && seed_buf.numel() >= 1,
-                "seed_buf must be a cuda int64 tensor");
-    auto* ptr = reinterpret_cast<unsigned long long*>(seed_buf.data_ptr<int64_t>());
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(bump_seed_kernel, dim3(1), dim3(1), 0, stream, ptr);
+    sample_gaussian_impl(out, mu, sigma, symmetric, 0, device_i64_scalar(seed_buf, "seed_buf"));
+    bump_seed(seed_buf);
 }
 
 // Apply x = mu + sigma*z from PRE-GENERATED standard normals (the noise
@@ -215,24 +208,16 @@ __global__ void affine_from_noise_kernel(T* __restrict__ out, const float* __res
 }
 
 void affine_from_noise(torch::Tensor out, torch::Tensor z, torch::Tensor mu, torch::Tensor sigma, bool symmetric) {
-    CHECK_GPU(out); CHECK_CONTIG(out); CHECK_GPU(z); CHECK_CONTIG(z);
-    const int64_t n = out.size(0), length = out.size(1);
-    TORCH_CHECK(!symmetric || n % 2 == 0, "symmetric affine needs even popsize");
-    const int64_t rows = symmetric ? n / 2 : n;
-    TORCH_CHECK(z.numel() == rows * length, "noise buffer shape mismatch");
-    TORCH_CHECK(z.scalar_type() == at::ScalarType::Float, "noise must be fp32");
+    const int64_t rows = check_sampling_operands(out, mu, sigma, symmetric);
+    const int64_t length = out.size(1);
+    check_operand_as(z, "z", out, at::ScalarType::Float, rows * length);
     const int threads = 256;
-    const int blocks = (int)std::min<int64_t>((rows * length + threads - 1) / threads, 256 * 8);
+    const int blocks = grid_for(rows * length, threads, 256 * 8);
     auto stream = at::cuda::getCurrentCUDAStream();
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half, out.scalar_type(), "affine_from_noise", [&] {
-        using T = scalar_t;
-        if (symmetric) {
-            hipLaunchKernelGGL((affine_from_noise_kernel<T, true>), dim3(blocks), dim3(threads), 0, stream,
-                               out.data_ptr<T>(), z.data_ptr<float>(), mu.data_ptr<T>(), sigma.data_ptr<T>(), rows, length);
-        } else {
-            hipLaunchKernelGGL((affine_from_noise_kernel<T, false>), dim3(blocks), dim3(threads), 0, stream,
-                               out.data_ptr<T>(), z.data_ptr<float>(), mu.data_ptr<T>(), sigma.data_ptr<T>(), rows, length);
-        }
+    DISPATCH_FLOAT_T(out, "affine_from_noise", {
+        auto kernel = symmetric ? affine_from_noise_kernel<T, true> : affine_from_noise_kernel<T, false>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream, out.data_ptr<T>(), z.data_ptr<float>(),
+                           mu.data_ptr<T>(), sigma.data_ptr<T>(), rows, length);
     });
 }
 
@@ -283,20 +268,23 @@ __global__ void es_grad_kernel(const T* __restrict__ x, const T* __restrict__ mu
 template <GradMode kMode>
 std::vector<torch::Tensor> es_grad_launch(torch::Tensor samples, torch::Tensor mu, torch::Tensor sigma,
                                           torch::Tensor weights) {
-    CHECK_GPU(samples); CHECK_CONTIG(samples);
+    check_primary(samples, "samples", 2);
     const int64_t n = samples.size(0), length = samples.size(1);
+    check_operand(mu, "mu", samples, length);
+    check_operand(sigma, "sigma", samples, length);
+    check_operand(weights, "weights", samples, n);
+    TORCH_CHECK(kMode != GradMode::kSymmetric || n % 2 == 0, "symmetric gradients need even popsize, got ", n);
     const int64_t rows = (kMode == GradMode::kSymmetric) ? n / 2 : n;
     auto opts = samples.options().dtype(torch::kFloat32);
     const int threads = 256;
-    const int col_blocks = (int)((length + threads - 1) / threads);
+    const int col_blocks = grid_for(length, threads);
     // fill the chip: >= ~1024 blocks total
     int row_chunks = 1;
     if (col_blocks < 1024) row_chunks = (int)std::min<int64_t>((1024 + col_blocks - 1) / col_blocks, std::max<int64_t>(rows / 8, 1));
     auto mu_grad = torch::empty({row_chunks, length}, opts);
     auto sigma_grad = torch::empty({row_chunks, length}, opts);
     auto stream = at::cuda::getCurrentCUDAStream();
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half, samples.scalar_type(), "es_gradients", [&] {
-        using T = scalar_t;
+    DISPATCH_FLOAT_T(samples, "es_gradients", {
         hipLaunchKernelGGL((es_grad_kernel<T, kMode>), dim3(col_blocks, row_chunks), dim3(threads), 0, stream,
                            samples.data_ptr<T>(), mu.data_ptr<T>(), sigma.data_ptr<T>(), weights.data_ptr<T>(),
                            mu_grad.data_ptr<float>(), sigma_grad.data_ptr<float>(), rows, n, length, row_chunks);
@@ -376,15 +364,15 @@ __global__ void clipup_clip_kernel(T* __restrict__ velocity, const float* __rest
 }
 
 void clipup_step(torch::Tensor velocity, torch::Tensor grad, double step_size, double max_speed, double momentum) {
-    CHECK_GPU(velocity); CHECK_CONTIG(velocity);
+    check_primary(velocity, "velocity", 1);
     const int64_t n = velocity.numel();
+    check_operand(grad, "grad", velocity, n);
     const int threads = 256;
-    const int blocks = (int)std::min<int64_t>((n + threads - 1) / threads, 1024);
+    const int blocks = grid_for(n, threads, 1024);
     // [0] gnorm², [1] vnorm², [2..2+blocks) per-block partials
     auto scratch = torch::empty({2 + blocks}, velocity.options().dtype(torch::kFloat32));
     auto stream = at::cuda::getCurrentCUDAStream();
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half, velocity.scalar_type(), "clipup_step", [&] {
-        using T = scalar_t;
+    DISPATCH_FLOAT_T(velocity, "clipup_step", {
         float* gnorm_sq = scratch.data_ptr<float>();
         float* vnorm_sq = gnorm_sq + 1;
         float* partials = gnorm_sq + 2;
@@ -398,20 +386,27 @@ void clipup_step(torch::Tensor velocity, torch::Tensor grad, double step_size, d
     });
 }
 
+// One element of the Adam ascent step, shared by both kernels below.
+template <typename T>
+__device__ __forceinline__ void adam_element(T* __restrict__ step_out, const T* __restrict__ grad, T* __restrict__ m,
+                                             T* __restrict__ v, int64_t i, float stepsize, float beta1, float beta2,
+                                             float epsilon, float bias1, float bias2) {
+    const float g = static_cast<float>(grad[i]);
+    const float m_new = fmaf(beta1, static_cast<float>(m[i]), (1.0f - beta1) * g);
+    const float v_new = fmaf(beta2, static_cast<float>(v[i]), (1.0f - beta2) * g * g);
+    m[i] = static_cast<T>(m_new);
+    v[i] = static_cast<T>(v_new);
+    step_out[i] = static_cast<T>(stepsize * (m_new / bias1) / (sqrtf(v_new / bias2) + epsilon));
+}
+
+// Bias corrections computed on the HOST (host powf): the two kernels stay
+// separate because the plain path's bits depend on which powf ran.
 template <typename T>
 __global__ void adam_kernel(T* __restrict__ step_out, const T* __restrict__ grad, T* __restrict__ m,
                             T* __restrict__ v, float stepsize, float beta1, float beta2, float epsilon,
                             float bias1, float bias2, int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float g = static_cast<float>(grad[i]);
-        const float m_new = fmaf(beta1, static_cast<float>(m[i]), (1.0f - beta1) * g);
-        const float v_new = fmaf(beta2, static_cast<float>(v[i]), (1.0f - beta2) * g * g);
-        m[i] = static_cast<T>(m_new);
-        v[i] = static_cast<T>(v_new);
-        const float mhat = m_new / bias1;
-        const float vhat = v_new / bias2;
-        step_out[i] = static_cast<T>(stepsize * mhat / (sqrtf(vhat) + epsilon));
-    }
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        adam_element(step_out, grad, m, v, i, stepsize, beta1, beta2, epsilon, bias1, bias2);
 }
 
 // Graph-safe Adam: the step count lives in a device buffer and is
@@ -424,55 +419,52 @@ __global__ void adam_graphsafe_kernel(T* __restrict__ step_out, const T* __restr
     const float t = (float)(*t_buf + 1);
     const float bias1 = 1.0f - powf(beta1, t);
     const float bias2 = 1.0f - powf(beta2, t);
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float g = static_cast<float>(grad[i]);
-        const float m_new = fmaf(beta1, static_cast<float>(m[i]), (1.0f - beta1) * g);
-        const float v_new = fmaf(beta2, static_cast<float>(v[i]), (1.0f - beta2) * g * g);
-        m[i] = static_cast<T>(m_new);
-        v[i] = static_cast<T>(v_new);
-        step_out[i] = static_cast<T>(stepsize * (m_new / bias1) / (sqrtf(v_new / bias2) + epsilon));
-    }
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        adam_element(step_out, grad, m, v, i, stepsize, beta1, beta2, epsilon, bias1, bias2);
 }
 
 __global__ void bump_step_kernel(long long* t_buf) { *t_buf += 1; }
 
+// Operand checks of both Adam entry points; returns the element count.
+static int64_t check_adam_operands(const torch::Tensor& step_out, const torch::Tensor& grad, const torch::Tensor& m,
+                                   const torch::Tensor& v) {
+    check_primary(step_out, "step_out", 1);
+    const int64_t n = step_out.numel();
+    check_operand(grad, "grad", step_out, n);
+    check_operand(m, "m", step_out, n);
+    check_operand(v, "v", step_out, n);
+    return n;
+}
+
 void adam_step_graphsafe(torch::Tensor step_out, torch::Tensor grad, torch::Tensor m, torch::Tensor v,
                          torch::Tensor t_buf, double stepsize, double beta1, double beta2, double epsilon) {
-    CHECK_GPU(step_out);
-    TORCH_CHECK(t_buf.is_cuda() && t_buf.scalar_type() == at::ScalarType::Long && t_buf.numel() >= 1,
-                "t_buf must be a cuda int64 tensor");
-    const int64_t n = step_out.numel();
+    const int64_t n = check_adam_operands(step_out, grad, m, v);
+    auto* t_ptr = reinterpret_cast<long long*>(device_i64_scalar(t_buf, "t_buf"));
     const int threads = 256;
-    const int blocks = (int)std::min<int64_t>((n + threads - 1) / threads, 2048);
+    const int blocks = grid_for(n, threads, 2048);
     auto stream = at::cuda::getCurrentCUDAStream();
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half, step_out.scalar_type(), "adam_graphsafe", [&] {
-        using T = scalar_t;
+    DISPATCH_FLOAT_T(step_out, "adam_graphsafe", {
         hipLaunchKernelGGL((adam_graphsafe_kernel<T>), dim3(blocks), dim3(threads), 0, stream, step_out.data_ptr<T>(),
-                           grad.data_ptr<T>(), m.data_ptr<T>(), v.data_ptr<T>(),
-                           reinterpret_cast<const long long*>(t_buf.data_ptr<int64_t>()), (float)stepsize,
+                           grad.data_ptr<T>(), m.data_ptr<T>(), v.data_ptr<T>(), t_ptr, (float)stepsize,
                            (float)beta1, (float)beta2, (float)epsilon, n);
     });
-    hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(1), 0, stream,
-                       reinterpret_cast<long long*>(t_buf.data_ptr<int64_t>()));
+    hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(1), 0, stream, t_ptr);
 }
 
 void adam_step(torch::Tensor step_out, torch::Tensor grad, torch::Tensor m, torch::Tensor v, int64_t step_count,
                double stepsize, double beta1, double beta2, double epsilon) {
-    CHECK_GPU(step_out);
-    const int64_t n = step_out.numel();
+    const int64_t n = check_adam_operands(step_out, grad, m, v);
     const int threads = 256;
-    const int blocks = (int)std::min<int64_t>((n + threads - 1) / threads, 2048);
+    const int blocks = grid_for(n, threads, 2048);
     const float bias1 = 1.0f - powf((float)beta1, (float)step_count);
     const float bias2 = 1.0f - powf((float)beta2, (float)step_count);
     auto stream = at::cuda::getCurrentCUDAStream();
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half, step_out.scalar_type(), "adam_step", [&] {
-        using T = scalar_t;
+    DISPATCH_FLOAT_T(step_out, "adam_step", {
         hipLaunchKernelGGL((adam_kernel<T>), dim3(blocks), dim3(threads), 0, stream, step_out.data_ptr<T>(),
                            grad.data_ptr<T>(), m.data_ptr<T>(), v.data_ptr<T>(), (float)stepsize, (float)beta1,
                            (float)beta2, (float)epsilon, bias1, bias2, n);
     });
 }
-
 
 // ---------------------------------------------------------------------------
 // K2: fused fitness ranking -> utility map (reference

@@ -17,17 +17,30 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include "check.h"
+
 namespace ea {
 
 constexpr int kMaxObjCache = 16;
 
+// a dominates b: no worse in every objective, strictly better in one
 __device__ __forceinline__ bool dominates_rows(const float* __restrict__ a, const float* __restrict__ b, int m) {
     bool ge_all = true, gt_any = false;
     for (int k = 0; k < m; ++k) {
-        ge_all &= (a[k] >= b[k]);
-        gt_any |= (a[k] > b[k]);
+        const float o = a[k];
+        ge_all &= (o >= b[k]);
+        gt_any |= (o > b[k]);
     }
     return ge_all && gt_any;
+}
+
+// Does `other` dominate a thread's own row? The own row is cached in the
+// register array `mine` when it fits (`cached`), else re-read from `own`
+// in global memory. Two calls on purpose: selecting one pointer between
+// the two (`me = cached ? mine : own`) sends the array to scratch.
+__device__ __forceinline__ bool dominated_by(const float* __restrict__ other, const float (&mine)[kMaxObjCache],
+                                             bool cached, const float* __restrict__ own, int m) {
+    return cached ? dominates_rows(other, mine, m) : dominates_rows(other, own, m);
 }
 
 __global__ void domination_counts_kernel(const float* __restrict__ utils, int* __restrict__ counts, int64_t n, int m) {
@@ -39,25 +52,7 @@ __global__ void domination_counts_kernel(const float* __restrict__ utils, int* _
         for (int k = 0; k < m; ++k) mine[k] = utils[j * m + k];
     }
     int count = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const float* other = utils + i * m;
-        bool ge_all = true, gt_any = false;
-        if (cached) {
-            for (int k = 0; k < m; ++k) {
-                const float o = other[k];
-                ge_all &= (o >= mine[k]);
-                gt_any |= (o > mine[k]);
-            }
-        } else {
-            const float* me = utils + j * m;
-            for (int k = 0; k < m; ++k) {
-                const float o = other[k];
-                ge_all &= (o >= me[k]);
-                gt_any |= (o > me[k]);
-            }
-        }
-        count += (ge_all && gt_any) ? 1 : 0;
-    }
+    for (int64_t i = 0; i < n; ++i) count += dominated_by(utils + i * m, mine, cached, utils + j * m, m) ? 1 : 0;
     counts[j] = count;
 }
 
@@ -74,9 +69,6 @@ __global__ void compact_front_kernel(int* __restrict__ counts, int64_t* __restri
                                      int* __restrict__ front_list, int* __restrict__ front_count, int64_t n,
                                      int64_t front_index) {
     const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (j == 0 && front_index == 0) {
-        // nothing: front_count reset is handled by reset_count_kernel
-    }
     if (j >= n) return;
     if (counts[j] == 0) {
         const int pos = atomicAdd(front_count, 1);
@@ -85,8 +77,6 @@ __global__ void compact_front_kernel(int* __restrict__ counts, int64_t* __restri
         counts[j] = -1;  // assigned marker
     }
 }
-
-__global__ void reset_count_kernel(int* __restrict__ front_count) { *front_count = 0; }
 
 __global__ void zero_counts_kernel(int* __restrict__ front_counts, int batch) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,17 +96,8 @@ __global__ void subtract_front_kernel(const float* __restrict__ utils, int* __re
     }
     const int fc = *front_count;
     int removed = 0;
-    for (int t = 0; t < fc; ++t) {
-        const float* other = utils + (int64_t)front_list[t] * m;
-        const float* me = cached ? mine : (utils + j * m);
-        bool ge_all = true, gt_any = false;
-        for (int k = 0; k < m; ++k) {
-            const float o = other[k];
-            ge_all &= (o >= me[k]);
-            gt_any |= (o > me[k]);
-        }
-        removed += (ge_all && gt_any) ? 1 : 0;
-    }
+    for (int t = 0; t < fc; ++t)
+        removed += dominated_by(utils + (int64_t)front_list[t] * m, mine, cached, utils + j * m, m) ? 1 : 0;
     counts[j] -= removed;
 }
 
@@ -127,7 +108,7 @@ torch::Tensor domination_counts(torch::Tensor utils) {
     const int m = (int)utils_f.size(1);
     auto counts = torch::empty({n}, utils_f.options().dtype(torch::kInt32));
     const int threads = 256;
-    const int blocks = (int)((n + threads - 1) / threads);
+    const int blocks = grid_for(n, threads);
     auto stream = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(domination_counts_kernel, dim3(blocks), dim3(threads), 0, stream, utils_f.data_ptr<float>(),
                        counts.data_ptr<int>(), n, m);
@@ -146,7 +127,7 @@ torch::Tensor pareto_ranks(torch::Tensor utils, int64_t min_assigned) {
     auto counts = domination_counts(utils_f);
     auto ranks = torch::full({n}, -1, utils_f.options().dtype(torch::kInt64));
     const int threads = 256;
-    const int blocks = (int)((n + threads - 1) / threads);
+    const int blocks = grid_for(n, threads);
     auto stream = at::cuda::getCurrentCUDAStream();
     // Peel in blind batches of kPeelBatch fronts with ONE host sync per
     // batch (a sync per front costs hundreds of round-trips at large N:
@@ -173,16 +154,11 @@ torch::Tensor pareto_ranks(torch::Tensor utils, int64_t min_assigned) {
         }
         const int64_t remaining = (counts >= 0).sum().item<int64_t>();  // one sync per batch
         if (remaining == 0) break;
-        if (n - remaining >= min_assigned) {
-            // enough solutions carry final ranks; lump the rest one past
-            // the last peeled front (they sort after every real front)
-            ranks.masked_fill_(counts >= 0, front_index);
-            break;
-        }
-        // numerical corner: no zero-count candidates among the remaining —
-        // assign the stragglers and stop
-        const int64_t candidates = (counts == 0).sum().item<int64_t>();
-        if (candidates == 0) {
+        // Stop when enough solutions carry final ranks, or in the numerical
+        // corner where no zero-count candidate is left among the remaining:
+        // lump the rest one past the last peeled front (they sort after
+        // every real front).
+        if (n - remaining >= min_assigned || (counts == 0).sum().item<int64_t>() == 0) {
             ranks.masked_fill_(counts >= 0, front_index);
             break;
         }
@@ -239,8 +215,12 @@ __global__ void mapelites_assign_kernel(const float* __restrict__ grid,   // [C]
 std::vector<torch::Tensor> mapelites_assign(torch::Tensor grid, torch::Tensor feats, torch::Tensor utils) {
     TORCH_CHECK(grid.is_cuda() && grid.dim() == 3 && grid.size(2) == 2, "grid must be (C, F, 2) on ROCm");
     TORCH_CHECK(feats.dim() == 2 && utils.dim() == 1, "feats (N, F), utils (N)");
+    check_same_device(feats, "feats", grid);
+    check_same_device(utils, "utils", grid);
     const int f = (int)grid.size(1);
     TORCH_CHECK(f <= kMaxFeat, "at most ", kMaxFeat, " feature dimensions");
+    TORCH_CHECK(feats.size(1) == f, "feats must have ", f, " columns, got ", feats.size(1));
+    TORCH_CHECK(utils.size(0) == feats.size(0), "utils must have ", feats.size(0), " entries, got ", utils.size(0));
     auto grid_f = grid.to(torch::kFloat32).contiguous();
     auto feats_f = feats.to(torch::kFloat32).contiguous();
     auto utils_f = utils.to(torch::kFloat32).contiguous();
@@ -248,7 +228,7 @@ std::vector<torch::Tensor> mapelites_assign(torch::Tensor grid, torch::Tensor fe
     auto best = torch::zeros({c_total}, grid.options().dtype(torch::kInt64));
     auto valid = torch::zeros({c_total}, grid.options().dtype(torch::kBool));
     const int threads = 256;
-    const int blocks = (int)((c_total + threads - 1) / threads);
+    const int blocks = grid_for(c_total, threads);
     auto stream = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(mapelites_assign_kernel, dim3(blocks), dim3(threads), 0, stream, grid_f.data_ptr<float>(),
                        feats_f.data_ptr<float>(), utils_f.data_ptr<float>(), best.data_ptr<int64_t>(),

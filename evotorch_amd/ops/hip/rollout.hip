@@ -56,8 +56,6 @@
 
 namespace ea {
 
-#define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be a ROCm tensor")
-
 // runtime member-index -> pointer select WITHOUT a runtime-indexed array
 // (which would demote to scratch memory — common-mistake #20); for
 // kMembers<=2 this folds to a single v_cndmask per operand.
@@ -486,14 +484,8 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
                              c10::optional<torch::Tensor> seed_buf) {
-    const unsigned long long* seed_ptr = nullptr;
-    if (seed_buf.has_value()) {
-        TORCH_CHECK(seed_buf->is_cuda() && seed_buf->scalar_type() == at::ScalarType::Long && seed_buf->numel() >= 1,
-                    "seed_buf must be a device int64 scalar");
-        seed_ptr = reinterpret_cast<const unsigned long long*>(seed_buf->data_ptr<int64_t>());
-    }
-    CHECK_GPU(params);
-    TORCH_CHECK(params.is_contiguous() && params.dim() == 2, "params must be contiguous [N][L]");
+    const unsigned long long* seed_ptr = seed_buf.has_value() ? device_i64_scalar(*seed_buf, "seed_buf") : nullptr;
+    check_primary(params, "params", 2);
     TORCH_CHECK(params.scalar_type() == at::ScalarType::Float, "params must be fp32");
     const int n = (int)params.size(0);
     const int O = (int)obs_dim, A = (int)act_dim, R = (int)rank, H = (int)policy_hidden;
@@ -501,6 +493,10 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
     TORCH_CHECK(params.size(1) == expected_len, "param length mismatch: got ", params.size(1), " expected ", expected_len);
     TORCH_CHECK(O % 2 == 0, "obs_dim must be even (bf16x2 packing)");
     TORCH_CHECK(H % 2 == 0, "policy_hidden must be even (bf16x2 packing)");
+    TORCH_CHECK(steps >= 0, "steps must be non-negative, got ", steps);
+    // the sum of the EnvBlob layout in rollout_common.h
+    check_operand(env_blob, "env_blob", params, (2 * (int64_t)R + A + 4) * O);
+    check_operand(obs_stats_out, "obs_stats_out", params, 2 * (int64_t)O);
     auto fitness = torch::empty({n}, params.options());
 
     RolloutArgs args;

@@ -6,7 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <c10/util/Exception.h>
+#include "check.h"
 
 namespace ea {
 
@@ -87,13 +87,6 @@ struct EnvBlob {
         : V(blob), U_T(V + (long)R * O), D2_T(U_T + (long)R * O), c(D2_T + (long)A * O), wr(c + O), mean(wr + O),
           std(mean + O) {}
 };
-
-// Kernels whose dynamic LDS exceeds the 64 KB default need the limit raised
-// once per kernel function.
-inline void allow_max_dynamic_lds(const void* kernel) {
-    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    TORCH_CHECK(err == hipSuccess, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: ", hipGetErrorString(err));
-}
 
 constexpr int kV7MembersPerBlock = 16;
 constexpr int kM7MembersPerBlock = 2;

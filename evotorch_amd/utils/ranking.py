@@ -114,9 +114,9 @@ def rank(fitnesses: torch.Tensor, ranking_method: Optional[str] = "raw", *, high
         and 1 < fitnesses.shape[0] <= 8192
         and ranking_method in _FUSED_METHODS
     ):
-        from ..ops.dispatch import _allow_eager_on_gpu, hip_required
+        from ..ops import hip_for
 
-        if not _allow_eager_on_gpu():
-            mod = hip_required()
+        mod = hip_for(fitnesses)
+        if mod is not None:
             return mod.fused_rank(fitnesses, _FUSED_METHODS[ranking_method], bool(higher_is_better))
     return f(fitnesses, higher_is_better=higher_is_better)

@@ -68,15 +68,10 @@ class TestSampleGaussian:
 @requires_gpu
 class TestEsGradients:
     def _eager(self, samples, mu, sigma, weights, symmetric):
-        import os
+        from evotorch_amd.ops import eager_on_gpu, es_gradients
 
-        os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"] = "1"
-        try:
-            from evotorch_amd.ops.dispatch import es_gradients
-
+        with eager_on_gpu():
             return es_gradients(samples, mu, sigma, weights, symmetric=symmetric)
-        finally:
-            os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"] = "0"
 
     @pytest.mark.parametrize("symmetric", [False, True])
     def test_matches_eager(self, C, symmetric):
@@ -92,8 +87,6 @@ class TestEsGradients:
         assert torch.allclose(sg, esg, rtol=1e-3, atol=1e-3)
 
     def test_snes_matches_eager(self, C):
-        import os
-
         torch.manual_seed(1)
         n, length = 256, 5000
         mu = torch.randn(length, device="cuda")
@@ -101,13 +94,10 @@ class TestEsGradients:
         samples = mu + sigma * torch.randn(n, length, device="cuda")
         weights = torch.randn(n, device="cuda")
         mg, sg = C.snes_gradients(samples, mu, sigma, weights)
-        os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"] = "1"
-        try:
-            from evotorch_amd.ops.dispatch import snes_gradients
+        from evotorch_amd.ops import eager_on_gpu, snes_gradients
 
+        with eager_on_gpu():
             emg, esg = snes_gradients(samples, mu, sigma, weights)
-        finally:
-            os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"] = "0"
         assert torch.allclose(mg, emg, rtol=1e-3, atol=1e-3)
         assert torch.allclose(sg, esg, rtol=1e-3, atol=1e-3)
 
@@ -250,24 +240,20 @@ class TestEndToEndGPU:
 @requires_gpu
 class TestParetoKernels:
     def test_matches_eager(self, C):
-        import os
-
         torch.manual_seed(7)
         n, m = 2000, 3
         utils = torch.randn(n, m, device="cuda")
         counts = C.domination_counts(utils)
         ranks = C.pareto_ranks(utils)
-        os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"] = "1"
-        try:
-            from evotorch_amd.core import _compute_pareto_ranks_eager
+        from evotorch_amd.core import _compute_pareto_ranks_eager
+        from evotorch_amd.ops import eager_on_gpu
 
+        with eager_on_gpu():
             eranks, _ = _compute_pareto_ranks_eager(utils, crowdsort=False)
             a = utils.unsqueeze(1)
             b = utils.unsqueeze(0)
             dom = (a >= b).all(dim=-1) & (a > b).any(dim=-1)
             ecounts = dom.sum(dim=0)
-        finally:
-            os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"] = "0"
         assert torch.equal(counts.to(torch.int64), ecounts.to(torch.int64))
         assert torch.equal(ranks, eranks)
 
@@ -425,9 +411,7 @@ def test_streaming_large_l_smoke():
 def test_kernel_fuzz_random_shapes():
     """Randomized-shape sweep of K1/K3 vs the eager fp32 reference:
     odd lengths, odd popsizes, both dtypes, both layouts."""
-    import os
-
-    from evotorch_amd.ops import es_gradients, sample_gaussian, snes_gradients
+    from evotorch_amd.ops import eager_on_gpu, es_gradients, sample_gaussian, snes_gradients
 
     torch.manual_seed(7)  # global cpu+cuda seed: draws below must not depend on test order
     g = torch.Generator().manual_seed(7)
@@ -459,11 +443,8 @@ def test_kernel_fuzz_random_shapes():
         if dtype == torch.float32:
             weights = torch.randn(n, device="cuda:0")
             gm, gs = es_gradients(out, mu, sigma, weights, symmetric=symmetric)
-            os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"] = "1"
-            try:
+            with eager_on_gpu():
                 gm_ref, gs_ref = es_gradients(out, mu, sigma, weights, symmetric=symmetric)
-            finally:
-                del os.environ["EVOTORCH_AMD_ALLOW_EAGER_GPU"]
             assert torch.allclose(gm, gm_ref, atol=1e-3, rtol=1e-3), (trial, (gm - gm_ref).abs().max())
             assert torch.allclose(gs, gs_ref, atol=1e-3, rtol=1e-3), (trial, (gs - gs_ref).abs().max())
 

@@ -190,3 +190,43 @@ def test_testing_helpers_surface():
     assert_eachclose(torch.full((4,), 7.0), 7.0)
     with pytest.raises(TestingError):
         assert_eachclose(torch.tensor([7.0, 8.0]), 7.0)
+
+
+def test_hip_for_cpu_tensor_is_none():
+    from evotorch_amd.ops import hip_for
+
+    assert hip_for(torch.zeros(3)) is None
+
+
+@pytest.mark.parametrize("before", [None, "0", "1"])
+@pytest.mark.parametrize("raises", [False, True])
+def test_eager_on_gpu_restores_environment(monkeypatch, before, raises):
+    import os
+
+    from evotorch_amd.ops import eager_on_gpu
+
+    name = "EVOTORCH_AMD_ALLOW_EAGER_GPU"
+    if before is None:
+        monkeypatch.delenv(name, raising=False)
+    else:
+        monkeypatch.setenv(name, before)
+    try:
+        with eager_on_gpu():
+            assert os.environ[name] == "1"
+            if raises:
+                raise KeyError("from the body")
+    except KeyError:
+        assert raises
+    assert os.environ.get(name) == before
+
+
+def test_seed_from_generator_is_a_function_of_the_generator_state():
+    from evotorch_amd.ops import seed_from_generator
+
+    cpu = torch.device("cpu")
+    a = torch.Generator().manual_seed(123)
+    b = torch.Generator().manual_seed(123)
+    seq_a = [seed_from_generator(a, cpu) for _ in range(5)]
+    seq_b = [seed_from_generator(b, cpu) for _ in range(5)]
+    assert seq_a == seq_b
+    assert len(set(seq_a)) == 5
