@@ -33,6 +33,7 @@ from typing import Optional
 import torch
 
 from ..distributions import ExpSeparableGaussian, SeparableGaussian, SymmetricSeparableGaussian
+from ..ops import seed_from_generator
 from ..optimizers import Adam, ClipUp
 from ..utils import ranking as _ranking
 from ..utils.misc import modify_tensor
@@ -76,7 +77,6 @@ class GraphedSearch:
 
         from .. import ops
         from ..core import SolutionBatch
-        from ..ops import seed_from_generator
 
         self._C = ops.hip_required()
         seed0 = seed_from_generator(problem.generator, problem.device)

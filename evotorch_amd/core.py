@@ -20,11 +20,14 @@ evaluated"; basic slicing returns shared-memory views.
 import logging
 import math
 import os
-from typing import Any, Callable, Iterable, List, Optional, Union
+from dataclasses import dataclass
+from typing import Any, Callable, Iterable, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
+from . import ops
+from .ops.dispatch import seed_from_generator, splitmix64
 from .utils import (
     Device,
     DType,
@@ -38,6 +41,7 @@ from .utils import (
     is_dtype_object,
     to_torch_dtype,
 )
+from .utils import ranking as ranking_mod
 from .utils.misc import ensure_tensor_length_and_dtype, split_workload
 from .utils.profiling import record_range
 
@@ -723,6 +727,19 @@ class Solution(Serializable):
 # ============================================================================
 
 
+@dataclass
+class _Pregen:
+    """Standard-normal noise drawn ahead of time on the side stream, and
+    the `(seed, row_offset)` it was drawn for (see `_schedule_pregen`)."""
+
+    z: torch.Tensor
+    zero: torch.Tensor
+    one: torch.Tensor
+    ready: "torch.cuda.Event"
+    seed: int
+    row_offset: int
+
+
 class Problem(TensorMakerMixin, Serializable):
     """The central object: objective sense(s), solution geometry, dtypes,
     device, RNG, bounds, evaluation dispatch, and (through an attached
@@ -734,6 +751,20 @@ class Problem(TensorMakerMixin, Serializable):
     are intentionally absent; SPMD rank topology comes from the launcher
     (torchrun) and `evotorch_amd.parallel`.
     """
+
+    # Attributes a clone (or a pickle) starts without: process-bound handles
+    # and scratch buffers, re-created on first use. `_graph_state` belongs to
+    # the hipGraph-capturing subclasses.
+    _NOT_CLONED = (
+        "_generator",
+        "_comm",
+        "_eval_pool",
+        "_grad_batch_cache",
+        "_stream_batch_cache",
+        "_pregen",
+        "_pregen_stream",
+        "_graph_state",
+    )
 
     def __init__(
         self,
@@ -846,6 +877,15 @@ class Problem(TensorMakerMixin, Serializable):
         self._spmd_gen_counter = 0
         self._defer_fused_reduce = False
         self._fused_reduce_requests: list = []
+        self._warned_no_interactions = False
+
+        # Scratch of the gradient paths, allocated on first use and never
+        # cloned (_NOT_CLONED): the reused sampling batch, the chunk-sized
+        # streaming batch, and the side-stream noise pre-generation
+        self._grad_batch_cache: Optional[SolutionBatch] = None
+        self._stream_batch_cache: Optional[SolutionBatch] = None
+        self._pregen: Optional[_Pregen] = None
+        self._pregen_stream: Optional["torch.cuda.Stream"] = None
 
     # -- configuration properties ---------------------------------------------
 
@@ -1038,8 +1078,6 @@ class Problem(TensorMakerMixin, Serializable):
         for a deterministic fitness function — is IDENTICAL for any world
         size that divides the popsize (SURVEY.md §7 "RNG discipline"). Rank
         seeds need not match; rank 0's generator decides."""
-        from .ops import seed_from_generator
-
         self._comm = comm
         base = seed_from_generator(self._generator, self._device)
         t = torch.tensor([base], dtype=torch.int64)
@@ -1050,16 +1088,12 @@ class Problem(TensorMakerMixin, Serializable):
 
     def _next_spmd_seed(self) -> int:
         """Next seed of the shared chain (all ranks advance in lockstep)."""
-        from .ops.dispatch import splitmix64
-
         self._spmd_gen_counter += 1
         return splitmix64(self._spmd_seed_base ^ (self._spmd_gen_counter * 0x9E3779B97F4A7C15))
 
     def _peek_spmd_seed(self, ahead: int = 1) -> int:
         """Look ahead in the shared seed chain without advancing it (the
         side-stream noise pre-generation needs next generation's seed)."""
-        from .ops.dispatch import splitmix64
-
         return splitmix64(self._spmd_seed_base ^ ((self._spmd_gen_counter + ahead) * 0x9E3779B97F4A7C15))
 
     # -- side-stream noise pre-generation (SURVEY.md §2.8 P2 overlap) --------
@@ -1072,45 +1106,43 @@ class Problem(TensorMakerMixin, Serializable):
     # direct counter-addressed sampling (both run fmaf(sigma, z, mu)).
 
     def _sample_with_pregen(self, distribution, values: torch.Tensor, seed: int, row_offset: int, dirs: int):
-        from . import ops
-
-        pg = getattr(self, "_pregen", None)
+        pg = self._pregen
         if (
             pg is not None
-            and pg["seed"] == seed
-            and pg["row_offset"] == row_offset
-            and pg["z"].shape == (dirs, self._solution_length)
+            and pg.seed == seed
+            and pg.row_offset == row_offset
+            and pg.z.shape == (dirs, self._solution_length)
         ):
-            torch.cuda.current_stream().wait_event(pg["ready"])
-            distribution.fill_from_noise(values, pg["z"])
+            torch.cuda.current_stream().wait_event(pg.ready)
+            distribution.fill_from_noise(values, pg.z)
         else:
             distribution.fill_counter_addressed(values, seed=seed, row_offset=row_offset)
 
     def _schedule_pregen(self, dirs: int, row_offset: int, seed: int):
-        from . import ops
-
         length = self._solution_length
-        if getattr(self, "_pregen_stream", None) is None:
+        if self._pregen_stream is None:
             self._pregen_stream = torch.cuda.Stream(device=self._device)
         stream = self._pregen_stream
-        pg = getattr(self, "_pregen", None)
-        if pg is None or pg["z"].shape != (dirs, length):
-            pg = {
-                "z": torch.empty((dirs, length), dtype=torch.float32, device=self._device),
-                "zero": torch.zeros(length, dtype=torch.float32, device=self._device),
-                "one": torch.ones(length, dtype=torch.float32, device=self._device),
-                "ready": torch.cuda.Event(),
-            }
+        pg = self._pregen
+        if pg is None or pg.z.shape != (dirs, length):
+            pg = _Pregen(
+                z=torch.empty((dirs, length), dtype=torch.float32, device=self._device),
+                zero=torch.zeros(length, dtype=torch.float32, device=self._device),
+                one=torch.ones(length, dtype=torch.float32, device=self._device),
+                ready=torch.cuda.Event(),
+                seed=seed,
+                row_offset=row_offset,
+            )
         # the side stream must not overwrite z while the main stream's
         # affine pass is still reading it
         consumed = torch.cuda.Event()
         consumed.record()
         with torch.cuda.stream(stream):
             stream.wait_event(consumed)
-            ops.sample_gaussian(pg["z"], pg["zero"], pg["one"], symmetric=False, seed=seed, row_offset=row_offset)
-            pg["ready"].record()
-        pg["seed"] = seed
-        pg["row_offset"] = row_offset
+            ops.sample_gaussian(pg.z, pg.zero, pg.one, symmetric=False, seed=seed, row_offset=row_offset)
+            pg.ready.record()
+        pg.seed = seed
+        pg.row_offset = row_offset
         self._pregen = pg
 
     def request_fused_reduce(self, tensor: torch.Tensor, callback) -> None:
@@ -1123,7 +1155,7 @@ class Problem(TensorMakerMixin, Serializable):
         if comm is None or comm.world_size <= 1:
             callback(tensor)
             return
-        if getattr(self, "_defer_fused_reduce", False):
+        if self._defer_fused_reduce:
             self._fused_reduce_requests.append((tensor, callback))
         else:
             comm.all_reduce_(tensor)
@@ -1370,10 +1402,20 @@ class Problem(TensorMakerMixin, Serializable):
         self._after_grad_status = self._after_grad_hook.accumulate_dict(result)
         return result
 
-    def _sample_popsize(self, distribution, popsize: int, num_interactions, popsize_max, ensure_even: bool):
-        if ensure_even and (popsize % 2 != 0):
-            popsize += 1
-        return popsize
+    def _effective_num_interactions(self, num_interactions: Optional[int]) -> Optional[int]:
+        """The adaptive-popsize threshold, or None (with a one-time warning)
+        when the problem reports no `last_eval_interaction_count` to compare
+        it against."""
+        if num_interactions is None or hasattr(self, "last_eval_interaction_count"):
+            return num_interactions
+        if not self._warned_no_interactions:
+            self._warned_no_interactions = True
+            _logger.warning(
+                "num_interactions=%s is set but %s does not report interaction counts "
+                "(no `last_eval_interaction_count`); the adaptive-popsize loop is disabled.",
+                num_interactions, type(self).__name__,
+            )
+        return None
 
     def _get_cached_grad_batch(self, popsize: int, device) -> "SolutionBatch":
         """Reusable sampling batch for the distribution-gradient path: a
@@ -1381,7 +1423,7 @@ class Problem(TensorMakerMixin, Serializable):
         caching allocator (measured: multi-second hipMalloc stalls at
         L=1e6, N=1e4); the batch is allocated once and re-sampled
         in place."""
-        cached = getattr(self, "_grad_batch_cache", None)
+        cached = self._grad_batch_cache
         if cached is not None and len(cached) == popsize and cached.device == torch.device(device):
             cached.forget_evals()
             return cached
@@ -1392,7 +1434,8 @@ class Problem(TensorMakerMixin, Serializable):
     def _sample_and_compute_gradients(
         self, distribution, popsize: int, obj_index: int, ranking_method, num_interactions=None, popsize_max=None, ensure_even_popsize: bool = False
     ) -> dict:
-        popsize = self._sample_popsize(distribution, popsize, num_interactions, popsize_max, ensure_even_popsize)
+        if ensure_even_popsize and popsize % 2 != 0:
+            popsize += 1
         batch = self._get_cached_grad_batch(popsize, self._device)
         with record_range("sample"):
             distribution.sample(out=batch.access_values(), generator=self._generator)
@@ -1401,14 +1444,10 @@ class Problem(TensorMakerMixin, Serializable):
         values = batch._values
         fitnesses = batch._evals[:, obj_index]
         total_popsize = popsize
-        if num_interactions is not None and not hasattr(self, "last_eval_interaction_count") and not getattr(self, "_warned_no_interactions", False):
-            self._warned_no_interactions = True
-            _logger.warning(
-                "num_interactions=%s is set but %s does not report interaction counts "
-                "(no `last_eval_interaction_count`); the adaptive-popsize loop is disabled.",
-                num_interactions, type(self).__name__,
-            )
-        if num_interactions is not None and hasattr(self, "last_eval_interaction_count"):
+        # asked after the first evaluation, which is where a problem may
+        # first set its interaction count
+        num_interactions = self._effective_num_interactions(num_interactions)
+        if num_interactions is not None:
             # adaptive popsize (reference core.py:3239-3274): keep sampling
             # extra sub-batches until the interaction threshold is reached
             interactions = int(getattr(self, "last_eval_interaction_count", 0) or 0)
@@ -1459,6 +1498,83 @@ class Problem(TensorMakerMixin, Serializable):
             cb(container.pop(f"__fused{i}"))
         return container
 
+    @staticmethod
+    def _shard_geometry(distribution, popsize: int, comm, ensure_even: bool) -> Tuple[int, int, int, int, bool]:
+        """``(world, rank, local_popsize, dirs_local, symmetric)``: rank r
+        owns directions [r·dirs_local, (r+1)·dirs_local) of the global
+        virtual population. A symmetric distribution always gets an even
+        local popsize (whole mirror pairs per rank)."""
+        world = comm.world_size if comm is not None else 1
+        rank = comm.rank if comm is not None else 0
+        symmetric = bool(getattr(distribution, "_symmetric", False))
+        local_popsize = popsize // world
+        if (ensure_even or symmetric) and local_popsize % 2 != 0:
+            local_popsize += 1
+        dirs_local = local_popsize // 2 if symmetric else local_popsize
+        return world, rank, local_popsize, dirs_local, symmetric
+
+    def _gradients_from_fitnesses(self, distribution, comm, sense: str, ranking_method, all_fit: torch.Tensor, blocks) -> dict:
+        """The shard-gradient protocol of `distributions.py`, from the
+        GLOBAL fitness vector to the gradients: rank once, accumulate raw
+        partial sums block by block in the order given, merge them (and any
+        deferred stat reductions) with one fused all-reduce when a Comm is
+        attached, finalize with global normalizers.
+
+        `blocks` yields ``(values, spans)``: a row block of this rank's
+        population and the ``(start, stop)`` positions of its rows in the
+        rank-major global vector — one span for a contiguous shard or
+        round, two (plus rows, minus rows) for a symmetric streamed chunk.
+        It is consumed lazily, one block at a time (the streamed path
+        regenerates every block into the same buffer)."""
+        ranking_used = ranking_method or "raw"
+        all_utils = ranking_mod.rank(all_fit, ranking_used, higher_is_better=(sense == "max"))
+        total = all_fit.shape[0]
+        elite_mode = "parenthood_ratio" in getattr(distribution, "parameters", {})
+
+        def rows_of(vector: torch.Tensor, spans) -> torch.Tensor:
+            if len(spans) == 1:
+                return vector[spans[0][0] : spans[0][1]]
+            return torch.cat([vector[start:stop] for start, stop in spans])
+
+        with record_range("partial_grads"):
+            if elite_mode:
+                # elite SET chosen from the GLOBAL utilities; each rank
+                # accumulates its local elite members' (Σx, Σx²); the sums
+                # (not a weighted gradient average — elite stats are
+                # non-linear in the shards) go through the fused all-reduce
+                num_elites = math.floor(total * float(distribution.parameters["parenthood_ratio"]))
+                global_elite = torch.zeros(total, dtype=torch.bool, device=all_utils.device)
+                global_elite[all_utils.argsort(descending=True)[:num_elites]] = True
+                sum_x, sum_x2 = distribution.accumulate_elite_sums_streamed(
+                    (values, rows_of(global_elite, spans)) for values, spans in blocks
+                )
+                sums = {"x": sum_x, "x2": sum_x2}
+            else:
+                w_all = distribution.prepare_weights_global(all_utils, ranking_used)
+                w_dtype = self._dtype if self._dtype.is_floating_point else torch.float32
+                sums = None
+                for values, spans in blocks:
+                    part = distribution.partial_grad_sums(values, rows_of(w_all, spans).to(dtype=w_dtype))
+                    if sums is None:
+                        sums = part
+                    else:
+                        for key in sums:
+                            sums[key] = sums[key] + part[key]
+
+        if comm is not None:
+            with record_range("grad_allreduce"):
+                sums = self._fused_allreduce_and_finalize(comm, sums)
+
+        if elite_mode:
+            grads = distribution.finalize_elite_gradients(sums["x"].to(torch.float64), sums["x2"].to(torch.float64), num_elites)
+        else:
+            grads = distribution.finalize_shard_gradients(sums, w_all, ranking_used)
+        return {
+            "gradients": grads,
+            "num_solutions": total,
+            "mean_eval": torch.nanmean(all_fit),  # 0-dim tensor: no host sync
+        }
+
     def _sample_and_compute_gradients_sharded(
         self, distribution, popsize: int, obj_index: int, ranking_method, comm, num_interactions=None, popsize_max=None, ensure_even_popsize: bool = False
     ) -> dict:
@@ -1479,27 +1595,8 @@ class Problem(TensorMakerMixin, Serializable):
         interaction count (one scalar all-reduce per round) reaches the
         threshold or `popsize_max` is hit.
         """
-        world = comm.world_size
-        rank = comm.rank
-        symmetric = bool(getattr(distribution, "_symmetric", False))
-        local_popsize = popsize // world
-        if (ensure_even_popsize or symmetric) and local_popsize % 2 != 0:
-            local_popsize += 1
-        dirs_local = local_popsize // 2 if symmetric else local_popsize
-        dirs_global = dirs_local * world
-        ranking_used = ranking_method or "raw"
-        sense = self._senses[obj_index]
-        from .utils import ranking as ranking_mod
-
-        if num_interactions is not None and not hasattr(self, "last_eval_interaction_count") and not getattr(self, "_warned_no_interactions", False):
-            self._warned_no_interactions = True
-            _logger.warning(
-                "num_interactions=%s is set but %s does not report interaction counts "
-                "(no `last_eval_interaction_count`); the adaptive-popsize loop is disabled.",
-                num_interactions, type(self).__name__,
-            )
-        if num_interactions is not None and not hasattr(self, "last_eval_interaction_count"):
-            num_interactions = None
+        world, rank, local_popsize, dirs_local, _symmetric = self._shard_geometry(distribution, popsize, comm, ensure_even_popsize)
+        num_interactions = self._effective_num_interactions(num_interactions)
 
         round_values: List[torch.Tensor] = []
         round_fits: List[torch.Tensor] = []
@@ -1550,60 +1647,20 @@ class Problem(TensorMakerMixin, Serializable):
                 break
 
         all_fit = round_fits[0] if len(round_fits) == 1 else torch.cat(round_fits)
-        all_utils = ranking_mod.rank(all_fit, ranking_used, higher_is_better=(sense == "max"))
-        elite_mode = "parenthood_ratio" in getattr(distribution, "parameters", {})
-
-        with record_range("partial_grads"):
-            if elite_mode:
-                num_elites = math.floor(total_popsize * float(distribution.parameters["parenthood_ratio"]))
-                global_elite = torch.zeros(total_popsize, dtype=torch.bool, device=all_utils.device)
-                global_elite[all_utils.argsort(descending=True)[:num_elites]] = True
-                # local-row elite mask: global row of my local row i in round
-                # k is k·local·world + rank·local + i (gather is rank-major)
-                mask = torch.zeros(len(round_values) * local_popsize, dtype=torch.bool, device=all_utils.device)
-                for k in range(len(round_values)):
-                    base = k * local_popsize * world + rank * local_popsize
-                    mask[k * local_popsize : (k + 1) * local_popsize] = global_elite[base : base + local_popsize]
-                sum_x, sum_x2 = distribution.accumulate_elite_sums_streamed(
-                    ((values, k * local_popsize, local_popsize) for k, values in enumerate(round_values)), mask
-                )
-                sums = {"x": sum_x, "x2": sum_x2}
-            else:
-                w_all = distribution.prepare_weights_global(all_utils, ranking_used)
-                w_dtype = self._dtype if self._dtype.is_floating_point else torch.float32
-                sums = None
-                for k, values in enumerate(round_values):
-                    base = k * local_popsize * world + rank * local_popsize
-                    my_w = w_all[base : base + local_popsize].to(dtype=w_dtype)
-                    part = distribution.partial_grad_sums(values, my_w)
-                    if sums is None:
-                        sums = part
-                    else:
-                        for key in sums:
-                            sums[key] = sums[key] + part[key]
-
-        with record_range("grad_allreduce"):
-            sums = self._fused_allreduce_and_finalize(comm, sums)
-
-        if elite_mode:
-            grads = distribution.finalize_elite_gradients(sums["x"].to(torch.float64), sums["x2"].to(torch.float64), num_elites)
-        else:
-            grads = distribution.finalize_shard_gradients(sums, w_all, ranking_used)
-        return {
-            "gradients": grads,
-            "num_solutions": total_popsize,
-            "mean_eval": torch.nanmean(all_fit),  # 0-dim tensor: no host sync
-        }
+        # global row of my local row i in round k is
+        # k·local·world + rank·local + i (the gather is rank-major)
+        blocks = []
+        for k, values in enumerate(round_values):
+            base = k * local_popsize * world + rank * local_popsize
+            blocks.append((values, ((base, base + local_popsize),)))
+        return self._gradients_from_fitnesses(distribution, comm, self._senses[obj_index], ranking_method, all_fit, blocks)
 
     def _get_stream_batch(self, popsize: int) -> "SolutionBatch":
-        cache = getattr(self, "_stream_batch_cache", None)
-        if cache is None:
-            cache = self._stream_batch_cache = {}
-        batch = cache.get(popsize)
-        if batch is None or batch.device != torch.device(self._device):
-            batch = self.generate_batch(popsize, empty=True)
-            cache.clear()  # at most the main chunk size + one tail size alive
-            cache[popsize] = batch
+        """The one chunk-sized scratch batch of the streamed path (replaced
+        when the tail chunk needs another size)."""
+        batch = self._stream_batch_cache
+        if batch is None or len(batch) != popsize or batch.device != torch.device(self._device):
+            batch = self._stream_batch_cache = self.generate_batch(popsize, empty=True)
         batch.forget_evals()
         return batch
 
@@ -1612,27 +1669,20 @@ class Problem(TensorMakerMixin, Serializable):
     ) -> dict:
         """Two-pass streaming ES gradients — see sample_and_compute_gradients.
 
-        Uses the same shard-gradient protocol as the non-streamed SPMD path
-        (prepare weights globally → raw partial sums per chunk → one fused
-        all-reduce → finalize with global normalizers), with the chunk axis
-        playing the role of extra shards. Rank r owns directions
+        Pass 1 and the chunk regenerator live here; from the fitness vector
+        on it is `_gradients_from_fitnesses`, the same tail as the
+        non-streamed SPMD path (prepare weights globally → raw partial sums
+        per block → one fused all-reduce → finalize with global
+        normalizers), with every regenerated chunk handed over as one more
+        block. Rank r owns directions
         [r·D/W, (r+1)·D/W) of the global virtual population, addressed by
         per-row philox streams from the shared seed chain — regenerable in
         pass 2 without storing the N×L population."""
         if not hasattr(distribution, "fill_counter_addressed"):
             raise ValueError(f"{type(distribution).__name__} does not support streamed gradients")
-        elite_mode = "parenthood_ratio" in getattr(distribution, "parameters", {})
-        from .ops import seed_from_generator
-        from .utils import ranking as ranking_mod
-
-        world = comm.world_size if comm is not None else 1
-        my_rank = comm.rank if comm is not None else 0
-        local_popsize = popsize // world
-        symmetric = bool(getattr(distribution, "_symmetric", False))
-        if symmetric and local_popsize % 2 != 0:
-            local_popsize += 1
-        directions = local_popsize // 2 if symmetric else local_popsize
+        world, my_rank, local_popsize, directions, symmetric = self._shard_geometry(distribution, popsize, comm, False)
         my_dir0 = my_rank * directions
+        my_row0 = my_rank * local_popsize  # of my fitnesses in the rank-major global vector
         # stream-per-row philox addressing: any chunk boundary is exact
         chunk_rows = min(chunk_rows, directions)
         seed = self._next_spmd_seed() if comm is not None else seed_from_generator(self._generator, self._device)
@@ -1660,15 +1710,11 @@ class Problem(TensorMakerMixin, Serializable):
             else:
                 fits[r0 : r0 + rows] = evals
 
-        # -- global ranking ---------------------------------------------------
+        # -- global fitness vector ---------------------------------------------
         if comm is not None and world > 1:
             all_fit = comm.all_gather_vector(fits)
         else:
             all_fit = fits
-        sense = self._senses[obj_index]
-        ranking_used = ranking_method or "raw"
-        all_utils = ranking_mod.rank(all_fit, ranking_used, higher_is_better=(sense == "max"))
-        total = world * local_popsize
 
         # -- pass 2: regenerate noise per chunk, accumulate exact gradients --
         def regen_chunks():
@@ -1676,48 +1722,15 @@ class Problem(TensorMakerMixin, Serializable):
                 batch = self._get_stream_batch(rows * 2 if symmetric else rows)
                 with record_range("stream_regen"):
                     distribution.fill_counter_addressed(batch.access_values(), seed=seed, row_offset=my_dir0 + r0)
-                yield batch._values, r0, rows
+                plus = (my_row0 + r0, my_row0 + r0 + rows)
+                if symmetric:
+                    minus = (my_row0 + directions + r0, my_row0 + directions + r0 + rows)
+                    yield batch._values, (plus, minus)
+                else:
+                    yield batch._values, (plus,)
 
         with record_range("stream_grad"):
-            if elite_mode:
-                # elite SET chosen from the GLOBAL utilities; each rank
-                # accumulates its local elite members' (Σx, Σx²); the sums
-                # (not a weighted gradient average — elite stats are
-                # non-linear in the shards) go through the fused all-reduce
-                num_elites = math.floor(total * float(distribution.parameters["parenthood_ratio"]))
-                global_elite = torch.zeros(total, dtype=torch.bool, device=all_utils.device)
-                global_elite[all_utils.argsort(descending=True)[:num_elites]] = True
-                my_elite = global_elite[my_rank * local_popsize : (my_rank + 1) * local_popsize]
-                sum_x, sum_x2 = distribution.accumulate_elite_sums_streamed(regen_chunks(), my_elite)
-                sums = {"x": sum_x, "x2": sum_x2}
-                if comm is not None:
-                    sums = self._fused_allreduce_and_finalize(comm, sums)
-                grads = distribution.finalize_elite_gradients(
-                    sums["x"].to(torch.float64), sums["x2"].to(torch.float64), num_elites)
-            else:
-                w_all = distribution.prepare_weights_global(all_utils, ranking_used)
-                w_dtype = self._dtype if self._dtype.is_floating_point else torch.float32
-                my_w = w_all[my_rank * local_popsize : (my_rank + 1) * local_popsize].to(dtype=w_dtype)
-                sums = None
-                for values_chunk, r0, rows in regen_chunks():
-                    if symmetric:
-                        w_c = torch.cat([my_w[r0 : r0 + rows], my_w[directions + r0 : directions + r0 + rows]])
-                    else:
-                        w_c = my_w[r0 : r0 + rows]
-                    part = distribution.partial_grad_sums(values_chunk, w_c)
-                    if sums is None:
-                        sums = part
-                    else:
-                        for key in sums:
-                            sums[key] = sums[key] + part[key]
-                if comm is not None:
-                    sums = self._fused_allreduce_and_finalize(comm, sums)
-                grads = distribution.finalize_shard_gradients(sums, w_all, ranking_used)
-        return {
-            "gradients": grads,
-            "num_solutions": total,
-            "mean_eval": torch.nanmean(all_fit),  # 0-dim tensor: no host sync
-        }
+            return self._gradients_from_fitnesses(distribution, comm, self._senses[obj_index], ranking_method, all_fit, regen_chunks())
 
     # -- functional adapter ---------------------------------------------------------
 
@@ -1731,7 +1744,7 @@ class Problem(TensorMakerMixin, Serializable):
     def _get_cloned_state(self, *, memo: dict) -> dict:
         state = {}
         for k, v in self.__dict__.items():
-            if k in ("_generator", "_comm", "_grad_batch_cache", "_pregen", "_pregen_stream", "_graph_state", "_eval_pool"):
+            if k in self._NOT_CLONED:
                 state[k] = None
             else:
                 state[k] = deep_clone(v, otherwise_deepcopy=True, memo=memo)

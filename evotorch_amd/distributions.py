@@ -128,7 +128,8 @@ class Distribution(TensorMakerMixin):
 
     # -- SPMD shard-gradient protocol ----------------------------------------
     #
-    # The sharded path (Problem._sample_and_compute_gradients_sharded) splits
+    # Problem._gradients_from_fitnesses (the one tail of the sharded and the
+    # streamed gradient path; a streamed chunk is one more row block) splits
     # the weight-dependent gradient into three phases so every normalization
     # uses GLOBAL quantities (a per-shard normalization would silently change
     # the merged gradient — ADVICE.md round-1 medium finding):
@@ -273,13 +274,13 @@ class SeparableGaussian(Distribution):
 
         ops.affine_from_noise(out, z, self.mu, self.sigma, symmetric=self._symmetric)
 
-    def accumulate_elite_sums_streamed(self, chunk_iter, is_elite: torch.Tensor):
+    def accumulate_elite_sums_streamed(self, chunk_iter):
         """Masked (Σx, Σx²) over elite rows, chunk by chunk (fp64 accum).
-        `is_elite` flags LOCAL rows; shards all-reduce the returned sums."""
+        `chunk_iter` yields ``(values_chunk, mask)`` with one elite flag per
+        row of the chunk; shards all-reduce the returned sums."""
         sum_x = torch.zeros_like(self.mu, dtype=torch.float64)
         sum_x2 = torch.zeros_like(self.mu, dtype=torch.float64)
-        for values_chunk, row0, rows in chunk_iter:
-            mask = is_elite[row0 : row0 + rows]
+        for values_chunk, mask in chunk_iter:
             if bool(mask.any()):
                 selected = values_chunk[mask].to(torch.float64)
                 sum_x += selected.sum(dim=0)
@@ -344,7 +345,7 @@ class SeparableGaussian(Distribution):
         from . import ops
 
         weights = self._centered_weights(weights, ranking_used)
-        mu_grad, sigma_grad = ops.es_gradients(samples, self.mu, self.sigma, weights, symmetric=False)
+        mu_grad, sigma_grad = ops.es_gradients(samples, self.mu, self.sigma, weights, symmetric=self._symmetric)
         return {
             "mu": self._divide_grad("mu", mu_grad, weights),
             "sigma": self._divide_grad("sigma", sigma_grad, weights),
@@ -411,18 +412,6 @@ class SymmetricSeparableGaussian(SeparableGaussian):
         plus = mu.unsqueeze(-2) + sigma.unsqueeze(-2) * z
         minus = 2.0 * mu.unsqueeze(-2) - plus
         return torch.cat([plus, minus], dim=-2)
-
-    def _compute_gradients(self, samples: torch.Tensor, weights: torch.Tensor, ranking_used: Optional[str]) -> dict:
-        if "parenthood_ratio" in self._parameters:
-            return self._elite_gradients(samples, weights)
-        from . import ops
-
-        weights = self._centered_weights(weights, ranking_used)
-        mu_grad, sigma_grad = ops.es_gradients(samples, self.mu, self.sigma, weights, symmetric=True)
-        return {
-            "mu": self._divide_grad("mu", mu_grad, weights),
-            "sigma": self._divide_grad("sigma", sigma_grad, weights),
-        }
 
 
 class ExpSeparableGaussian(SeparableGaussian):

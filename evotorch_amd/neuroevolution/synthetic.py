@@ -14,6 +14,7 @@ from typing import Optional
 import torch
 
 from ..core import Problem, SolutionBatch
+from ..ops import seed_from_generator
 from .runningnorm import ObsNormLayer, RunningNorm
 from .synthetic_env import SyntheticEnvSpec, rollout_eager
 
@@ -47,6 +48,7 @@ class SyntheticRolloutProblem(Problem):
         self._obs_norm = RunningNorm(shape=spec.obs_dim, device=device)
         self._decrease_rewards_by = float(decrease_rewards_by)
         self._pending_stats = None
+        self._graph_seed_buf: Optional[torch.Tensor] = None  # device seed chain, set by enable_graph_mode
         self.last_eval_interaction_count = 0
         self._total_interactions = 0
         self._episode_count = 0
@@ -85,9 +87,7 @@ class SyntheticRolloutProblem(Problem):
         the problem's own generator."""
         if self._device.type != "cuda":
             return
-        if getattr(self, "_graph_seed_buf", None) is None:
-            from ..ops import seed_from_generator
-
+        if self._graph_seed_buf is None:
             seed0 = seed_from_generator(self._generator, self._device)
             self._graph_seed_buf = torch.tensor([seed0], dtype=torch.int64, device=self._device)
 
@@ -95,9 +95,7 @@ class SyntheticRolloutProblem(Problem):
         values = batch.access_values(keep_evals=True)
         n = len(batch)
         spec = self._spec
-        from ..ops import seed_from_generator
-
-        seed_buf = getattr(self, "_graph_seed_buf", None)
+        seed_buf = self._graph_seed_buf
         init_seed = 0 if seed_buf is not None else seed_from_generator(self._generator, self._device) & 0x7FFFFFFF
         member_offset = 0
         comm = self._comm

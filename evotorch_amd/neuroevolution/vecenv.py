@@ -23,6 +23,7 @@ from torch import nn
 
 from ..core import SolutionBatch
 from ..models import Policy
+from ..ops import seed_from_generator
 from .neproblem import NEProblem
 from .runningnorm import RunningNorm
 from .synthetic_env import SyntheticEnvSpec
@@ -363,9 +364,6 @@ class VecEnvNE(NEProblem):
             self._policy = self.make_functional_policy()
         policy = self._policy
         params = batch.access_values(keep_evals=True).to(device, torch.float32)
-
-        from ..ops import seed_from_generator
-
         episode_seed = seed_from_generator(self._generator, self._device) & 0x7FFFFFFF
         max_steps = self._max_num_steps or getattr(env.spec, "episode_length", None) or 1000
 

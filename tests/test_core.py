@@ -159,6 +159,25 @@ def test_problem_pickling():
     prob2.evaluate(b2)
 
 
+def test_clone_drops_gradient_scratch_batches():
+    """The chunk-sized stream batch and the reused gradient batch are
+    scratch: a clone starts without them and allocates its own."""
+    from evotorch_amd.distributions import SymmetricSeparableGaussian
+
+    dist = SymmetricSeparableGaussian({"mu": torch.zeros(8), "sigma": torch.ones(8)})
+    prob = make_problem()
+    prob.sample_and_compute_gradients(dist, 16, ranking_method="centered", chunk_rows=4)
+    prob.sample_and_compute_gradients(dist, 16, ranking_method="centered")
+    assert prob._stream_batch_cache is not None and prob._grad_batch_cache is not None
+    clone = prob.clone()
+    assert not clone._stream_batch_cache
+    assert clone._grad_batch_cache is None
+    result = clone.sample_and_compute_gradients(dist, 16, ranking_method="centered", chunk_rows=4)
+    for k in ("mu", "sigma"):
+        assert torch.isfinite(result["gradients"][k]).all()
+    assert clone._stream_batch_cache is not prob._stream_batch_cache
+
+
 def test_object_dtype_problem():
     class PermProblem(Problem):
         def __init__(self):

@@ -478,6 +478,59 @@ def test_pregen_overlap_bitwise_equals_direct_sampling():
 
 
 @requires_gpu
+@pytest.mark.parametrize("length", [7, 16])
+@pytest.mark.parametrize("family", ["symmetric", "snes"])
+def test_sharded_pregen_and_streamed_paths_agree_on_gpu(family, length):
+    """World 1 on the GPU: the sharded call (second generation: noise
+    pre-generated on the side stream + affine pass) and the streamed call
+    with one chunk (direct counter-addressed sampling, twice) share one
+    gradient tail and the same seed chain. The gradient reductions use no
+    float atomics, so the two agree bit for bit.
+
+    Measured at commit 5246286 (before the two paths shared a tail): largest
+    absolute deviation 0.0 for mu, sigma and mean_eval in all four cases."""
+    from evotorch_amd import Problem
+    from evotorch_amd.decorators import vectorized
+    from evotorch_amd.distributions import ExpSeparableGaussian, SymmetricSeparableGaussian
+    from evotorch_amd.parallel.comm import Comm
+
+    @vectorized
+    def sphere(x):
+        return (x**2).sum(-1)
+
+    popsize = 24
+    g = torch.Generator().manual_seed(length)
+    params = {"mu": torch.randn(length, generator=g).cuda(), "sigma": (torch.rand(length, generator=g) + 0.5).cuda()}
+    if family == "symmetric":
+        dist = SymmetricSeparableGaussian({**params, "divide_mu_grad_by": "num_directions", "divide_sigma_grad_by": "num_directions"})
+        directions = popsize // 2
+    else:
+        dist = ExpSeparableGaussian(params)
+        directions = popsize
+
+    def two_generations(chunk_rows):
+        prob = Problem("min", sphere, solution_length=length, initial_bounds=(-1, 1), seed=3, device="cuda:0")
+        prob.use_comm(Comm(device=torch.device("cuda", 0)))
+        out = [prob.sample_and_compute_gradients(dist, popsize, ranking_method="centered", chunk_rows=chunk_rows) for _ in range(2)]
+        torch.cuda.synchronize()
+        return prob, out
+
+    prob_sharded, sharded = two_generations(None)
+    _, streamed = two_generations(directions)
+    assert prob_sharded._pregen is not None  # generation 2 consumed pre-generated noise
+    deviations = {}
+    for gen, (a, b) in enumerate(zip(sharded, streamed)):
+        for k in ("mu", "sigma"):
+            deviations[(gen, k)] = float((a["gradients"][k] - b["gradients"][k]).abs().max())
+        deviations[(gen, "mean_eval")] = float((a["mean_eval"] - b["mean_eval"]).abs())
+    print(f"sharded-vs-streamed max abs deviation [{family}, L={length}]: {deviations}")
+    for a, b in zip(sharded, streamed):
+        for k in ("mu", "sigma"):
+            assert torch.equal(a["gradients"][k], b["gradients"][k]), (k, deviations)
+        assert torch.equal(a["mean_eval"], b["mean_eval"]), deviations
+
+
+@requires_gpu
 def test_sharded_world1_pgpe_with_overlap_improves():
     """The SPMD path (counter-addressed sampling + pregen overlap + fused
     all-reduce) at world size 1 on a real GPU: descends and is

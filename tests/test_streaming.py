@@ -61,7 +61,7 @@ def test_streamed_gradients_plain_separable():
 
 
 def test_streamed_rejects_unsupported_configs():
-    # elite streaming is single-rank only; num_interactions unsupported; chunk_rows >= 1
+    # num_interactions unsupported; chunk_rows >= 1
     dist = SymmetricSeparableGaussian({"mu": torch.zeros(4), "sigma": torch.ones(4)})
     with pytest.raises(ValueError):
         make_problem(length=4).sample_and_compute_gradients(dist, 8, chunk_rows=0)
@@ -96,9 +96,47 @@ def test_streaming_requires_distributed_mode():
              stdev_init=1.0, grad_chunk_rows=4)
 
 
+def _dist_plain_separable(length):
+    return SeparableGaussian({"mu": torch.zeros(length), "sigma": torch.ones(length),
+                              "divide_mu_grad_by": "num_solutions", "divide_sigma_grad_by": "weight_stdev"})
+
+
+def _dist_snes(length):
+    return ExpSeparableGaussian({"mu": torch.zeros(length), "sigma": torch.ones(length)})
+
+
+def _dist_elite(length):
+    return SeparableGaussian({"mu": torch.zeros(length), "sigma": torch.ones(length), "parenthood_ratio": 0.25})
+
+
+@pytest.mark.parametrize("ranking", ["centered", "raw", "nes"])
+@pytest.mark.parametrize("make_dist", [sym_dist, _dist_plain_separable, _dist_snes, _dist_elite])
+def test_sharded_and_streamed_paths_agree_exactly(make_dist, ranking):
+    """At world 1 the sharded call and the streamed call with one chunk
+    (chunk_rows = directions per rank) draw the same chain seed and hand one
+    identical block to the same gradient tail, so they agree bit for bit.
+    L = 7 exercises the philox 4-wide tail."""
+    from evotorch_amd.parallel import init_comm
+
+    length, popsize = 7, 24
+    dist = make_dist(length)
+    directions = popsize // 2 if dist._symmetric else popsize
+    results = []
+    for chunk_rows in (None, directions):
+        prob = make_problem(length=length, seed=17)
+        prob.use_comm(init_comm())
+        results.append(prob.sample_and_compute_gradients(dist, popsize, ranking_method=ranking, chunk_rows=chunk_rows))
+    sharded, streamed = results
+    assert sharded["num_solutions"] == streamed["num_solutions"] == popsize
+    for k in ("mu", "sigma"):
+        assert torch.equal(sharded["gradients"][k], streamed["gradients"][k]), k
+    assert torch.equal(sharded["mean_eval"], streamed["mean_eval"])
+
+
 def test_odd_length_chunk_alignment():
-    """L % 4 != 0: chunk_rows is auto-aligned to a multiple of 4 so every
-    chunk starts on a philox counter boundary."""
+    """L % 4 != 0: chunk boundaries may fall anywhere, because the noise is
+    addressed per row (one philox stream per direction), not per flat
+    element; any chunking reproduces the single-chunk gradient."""
     r1 = make_problem(length=7, seed=13).sample_and_compute_gradients(sym_dist(7), 24, ranking_method="centered", chunk_rows=3)
     r2 = make_problem(length=7, seed=13).sample_and_compute_gradients(sym_dist(7), 24, ranking_method="centered", chunk_rows=12)
     for k in ("mu", "sigma"):
