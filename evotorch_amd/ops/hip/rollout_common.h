@@ -22,7 +22,11 @@ __device__ __forceinline__ float b2f(__bf16 v) { return (float)v; }
 // libm tanhf is branchy code on the hot path.
 __device__ __forceinline__ float tanh_fast(float x) {
     const float xc = fminf(fmaxf(x, -15.0f), 15.0f);
-    const float e = __expf(2.0f * xc);
+    // e^(2x) = 2^(x · 2·log2(e)) with the doubling folded into the constant
+    // (0x4038aa3b, exactly twice the log2(e) that __expf multiplies by):
+    // one multiply feeds v_exp_f32, and the product rounds to the same bits
+    // as __expf(2.0f * xc) since 2·xc is exact
+    const float e = __builtin_amdgcn_exp2f(xc * __builtin_bit_cast(float, 0x4038aa3bu));
     // v_rcp_f32 (~1 ulp) instead of an IEEE divide: the result is bf16-
     // quantized immediately, so the 2^-23-level rcp error is invisible
     return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);

@@ -36,8 +36,26 @@
 // one fma chain in action order, sliced under the GEMM2 epilogue. No ds_bpermute shuffles in the
 // loop (see reduce32_dpp).
 //
+// GEMM1 is wave 0's alone: 24 LDS fragment reads and 12 MFMAs per step,
+// ahead of the wave's policy share. It is NOT hidden under the policy
+// work: the compiler keeps it as an exec-masked region that wave 0 runs
+// through (each MFMA behind its operands' s_waitcnt) before its first
+// v_dot2, and the other seven waves wait for wave 0 at the barrier.
+// Issuing the MFMAs inside wave 0's dot-product loop (two per 17 v_dot2,
+// operands read an iteration ahead, order pinned with sched_group_barrier,
+// scalar wave test) was built and measured 70 µs per launch SLOWER
+// (T = 1000), so GEMM1 stays a block of its own.
+//
 // GEMM2 phase: hact is the MFMA A operand, [U;D2] the B operand; a lane's
-// D fragment is one obs column of four members.
+// D fragment is one obs column of four members. The epilogue quantizes
+// and normalizes the four rows in pairs (one packed bf16 conversion per
+// pair, 16-bit LDS stores of its halves).
+//
+// The episode loop exists twice: a block whose 16 slots are all live
+// (every block when the population is a multiple of 16) runs a body
+// without per-member guards or statistics masks, the last partial block
+// the masked body. A live member's instruction sequence is the same in
+// both.
 //
 // Every sum keeps the order it had before the transposing reduction, so
 // results are bit-identical to the full-width version; and a member's
@@ -59,6 +77,8 @@
 //   D(16×16): col = lane&15,  row = (lane>>4)*4 + reg
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "philox.h"
 #include "rollout_common.h"
@@ -97,6 +117,22 @@ __device__ __forceinline__ float row_pair_add(float x) {
     // scalars first: __builtin_bit_cast applied to r[1] directly reads r[0]
     const unsigned from_row0 = r[0], from_row1 = r[1];
     return __builtin_bit_cast(float, from_row0) + __builtin_bit_cast(float, from_row1);
+}
+
+typedef __attribute__((ext_vector_type(2))) float floatx2;
+
+// Two floats to bf16 with ONE v_cvt_pk_bf16_f32 (a scalar f2b spends the
+// same instruction on one value); x is the low half.
+__device__ __forceinline__ bf16x2 f2b_pair(float lo, float hi) {
+    const floatx2 v = {lo, hi};
+    return __builtin_convertvector(v, bf16x2);
+}
+
+// ... and back: the low half shifts up, the high half is masked in place.
+__device__ __forceinline__ floatx2 b2f_pair(bf16x2 v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const floatx2 f = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
+    return f;
 }
 
 // Compile-time geometry and the dynamic-LDS layout (byte offsets), stated
@@ -268,13 +304,20 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     float stat_sum[kTilesPerWave] = {};        // per owned obs column
     float stat_sumsq[kTilesPerWave] = {};
 
-    // A-frag rows beyond the stored kM member rows alias row 0 (safe reads;
-    // their outputs are masked in every epilogue).
-    const int a_row = (g2_row < kM) ? g2_row : 0;
+    // the 16 rows of an MFMA A/D fragment are exactly the block's member slots
+    static_assert(kM == 16, "GEMM1/GEMM2 fragments address member rows 0..15 unguarded");
+    const int a_row = g2_row;
 
+    // The episode loop, instantiated twice: kFull for a block whose kM
+    // member slots are all live (every block of a population that is a
+    // multiple of kM), without the per-member guards; and the masked body
+    // for the last, partial block. A live member runs the same instruction
+    // sequence in both, so its results do not depend on which one it is in.
+    auto episode = [&](auto full) __attribute__((always_inline)) {
+    constexpr bool kFull = decltype(full)::value;
     for (int t = 0; t < args.steps; ++t) {
-        // ===== GEMM1 (wave 0): h = obs @ Vᵀ — issued before the policy VALU
-        // work so the MFMA chain executes on the MAI pipe underneath it =====
+        // ===== GEMM1 (wave 0): h = obs @ Vᵀ, before the wave's policy share
+        // (not overlapped with it, see the header) =====
         floatx4 h_acc = {0.f, 0.f, 0.f, 0.f};
         if (wave == 0) {
             // two accumulator chains: a single accumulator serializes 12
@@ -298,7 +341,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
             float acc[A_MAX];
 #pragma unroll
             for (int a = 0; a < A_MAX; ++a) acc[a] = 0.0f;
-            if (my_member < live) {
+            if (kFull || my_member < live) {
                 const __bf16* on = obsn_l + my_member * OPS + l32 * kChunk;
 #pragma unroll
                 for (int p = 0; p < kChunk / 2; ++p) {
@@ -341,7 +384,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
             for (int r = 0; r < 4; ++r) {
                 // D: col = h-index, row = member
                 const int m = c_row0 + r;
-                if (m < kM) hact_l[m * KS + c_col] = f2b(h_acc[r]);
+                hact_l[m * KS + c_col] = f2b(h_acc[r]);
             }
         }
         __syncthreads();
@@ -354,7 +397,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = c_row0 + r;
-                a16[r] = b2f(hact_l[((m < kM) ? m : 0) * KS + 32]);
+                a16[r] = b2f(hact_l[m * KS + 32]);
             }
             // Σa² of the step, as ONE fma chain in action order per member
             // (the summation order the fitness has always had), from the
@@ -382,22 +425,46 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 const float wrv = wr_l[col];
                 const float mv = mean_l[col];
                 const float iv = istd_l[col];
-                const bool col_in = col < O;
                 float ssum = 0.0f, ssq = 0.0f;
+                float o_row[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int m = c_row0 + r;
                     const float o_new = tanh_fast(fmaf(a16[r], d2l, acc[r]) + cv);
                     fit_part[r] = fmaf(wrv, o_new, fit_part[r]);
-                    if (m < live && col_in) {
+                    // Statistics over the live rows. Pad columns (col >= O)
+                    // need no mask: their c, d2last and [U;D2] row are 0, so
+                    // o_new = tanh_fast(0) = +0 exactly, and their sums are
+                    // never stored. Row 0 starts the sums: 0 + o and
+                    // fma(o, o, 0) give the same bits (tanh_fast never
+                    // returns -0) but cost an op each.
+                    const bool in = kFull || m < live;
+                    if (r == 0) {
+                        ssum = in ? o_new : 0.0f;
+                        ssq = in ? o_new * o_new : 0.0f;
+                    } else if (in) {
+                        // o_new is a product ((e - 1) · rcp): without this the
+                        // unmasked body contracts it into the add as one fma
+                        // (one rounding instead of two), and the sums change bits
+#pragma clang fp contract(off)
                         ssum += o_new;
                         ssq = fmaf(o_new, o_new, ssq);
                     }
-                    if (m < kM) {
-                        const __bf16 ob = f2b(o_new);
-                        obs_l[m * OPS + col] = ob;
-                        obsn_l[m * OPS + col] = f2b((b2f(ob) - mv) * iv);
-                    }
+                    o_row[r] = o_new;
+                }
+                // quantize, normalize and store the rows in pairs: one packed
+                // conversion serves two rows (same values as row by row)
+#pragma unroll
+                for (int r = 0; r < 4; r += 2) {
+                    const bf16x2 ob = f2b_pair(o_row[r], o_row[r + 1]);
+                    const floatx2 of = b2f_pair(ob);
+                    const bf16x2 on = f2b_pair((of.x - mv) * iv, (of.y - mv) * iv);
+                    __bf16* po = obs_l + (c_row0 + r) * OPS + col;
+                    __bf16* pn = obsn_l + (c_row0 + r) * OPS + col;
+                    po[0] = ob.x;
+                    po[OPS] = ob.y;
+                    pn[0] = on.x;
+                    pn[OPS] = on.y;
                 }
                 stat_sum[tw] += ssum;
                 stat_sumsq[tw] += ssq;
@@ -410,6 +477,9 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
         }
         __syncthreads();
     }
+    };
+    if (live == kM) episode(std::true_type{});
+    else episode(std::false_type{});
 
     // ---- wrap-up ----
     // Deterministic fitness reduction (no float atomics — the kernel must
