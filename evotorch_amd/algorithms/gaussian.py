@@ -13,10 +13,12 @@ gaussian.py:35-1404. Two execution modes:
 """
 
 import math
+import numbers
 from typing import Optional
 
 import torch
 
+from .. import ops
 from ..core import Problem, SolutionBatch
 from ..distributions import (
     Distribution,
@@ -25,7 +27,7 @@ from ..distributions import (
     SeparableGaussian,
     SymmetricSeparableGaussian,
 )
-from ..optimizers import get_optimizer_class
+from ..optimizers import ClipUp, get_optimizer_class
 from ..utils import RealOrVector, modify_tensor, to_stdev_init
 from ..utils.misc import ensure_tensor_length_and_dtype
 from ..utils.profiling import record_range
@@ -108,6 +110,13 @@ class GaussianSearchAlgorithm(SearchAlgorithm, SinglePopulationAlgorithmMixin):
                 return None
             return ensure_tensor_length_and_dtype(x, problem.solution_length, problem.dtype, about=about, allow_scalar=True, device=problem.device)
 
+        # the bounds as plain numbers where all of them were given so (or
+        # not at all): the one-launch update takes scalars only
+        bounds = (stdev_min, stdev_max, stdev_max_change)
+        if all(x is None or (isinstance(x, numbers.Real) and not isinstance(x, bool)) for x in bounds):
+            self._stdev_bound_scalars = tuple(None if x is None else float(x) for x in bounds)
+        else:
+            self._stdev_bound_scalars = None
         self._stdev_min = opt_length_tensor(stdev_min, "stdev_min")
         self._stdev_max = opt_length_tensor(stdev_max, "stdev_max")
         self._stdev_max_change = opt_length_tensor(stdev_max_change, "stdev_max_change")
@@ -231,7 +240,49 @@ class GaussianSearchAlgorithm(SearchAlgorithm, SinglePopulationAlgorithmMixin):
             self._update_distribution(gradients)
         self._fill_and_eval_pop()
 
+    def _update_distribution_fused(self, gradients: dict) -> bool:
+        """The whole update as ONE launch (ops.gaussian_clipup_update) where
+        it applies: fp32 ROCm parameters, a plain separable Gaussian, exactly
+        ClipUp, scalar stdev bounds, L within the kernel's bound. Returns
+        False, having done nothing, for anything else; `_update_distribution`
+        then runs its chain, which gives the same bits."""
+        dist = self._distribution
+        opt = self._optimizer
+        if type(dist) not in (SeparableGaussian, SymmetricSeparableGaussian) or type(opt) is not ClipUp:
+            return False
+        if self._stdev_bound_scalars is None:
+            return False
+        mu, sigma = dist.parameters["mu"], dist.parameters["sigma"]
+        velocity = opt._velocity
+        if (
+            mu.numel() > ops.GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH
+            or sigma.dtype != torch.float32
+            or velocity.dtype != torch.float32
+            or velocity.device != mu.device
+            or ops.fused_tail_for(mu) is None
+        ):
+            return False
+        stdev_min, stdev_max, stdev_max_change = self._stdev_bound_scalars
+        new_mu, new_sigma = ops.gaussian_clipup_update(
+            mu,
+            sigma,
+            velocity,
+            gradients["mu"].to(dtype=torch.float32, device=mu.device),
+            gradients["sigma"].to(dtype=torch.float32, device=mu.device),
+            step_size=opt._stepsize,
+            max_speed=opt._max_speed,
+            momentum=opt._momentum,
+            sigma_lr=self._stdev_learning_rate,
+            stdev_min=stdev_min,
+            stdev_max=stdev_max,
+            stdev_max_change=stdev_max_change,
+        )
+        self._distribution = dist.modified_copy(mu=new_mu, sigma=new_sigma)
+        return True
+
     def _update_distribution(self, gradients: dict):
+        if self._update_distribution_fused(gradients):
+            return
         controlled = (self._stdev_min is not None) or (self._stdev_max is not None) or (self._stdev_max_change is not None)
         old_sigma = self._distribution.parameters.get("sigma", None) if controlled else None
 

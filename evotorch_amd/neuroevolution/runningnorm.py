@@ -99,13 +99,18 @@ class RunningNorm:
             self._has_data = self._has_data or x._has_data
             return
         if isinstance(x, tuple) and len(x) == 3:
+            from ..ops import obsnorm_merge_
+
             count, s, ss = x
-            if isinstance(count, torch.Tensor):
-                self._count += count.to(self._count.device, torch.float64)
-            else:
-                self._count += float(count)
-            self._sum += torch.as_tensor(s, dtype=self._dtype, device=self._device)
-            self._sum_sq += torch.as_tensor(ss, dtype=self._dtype, device=self._device)
+            # one launch on fp32 ROCm state, the three adds anywhere else
+            obsnorm_merge_(
+                self._count,
+                self._sum,
+                self._sum_sq,
+                count,
+                torch.as_tensor(s, dtype=self._dtype, device=self._device),
+                torch.as_tensor(ss, dtype=self._dtype, device=self._device),
+            )
             self._has_data = True
             return
         x = torch.as_tensor(x, dtype=self._dtype, device=self._device)

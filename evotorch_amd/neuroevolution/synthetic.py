@@ -22,6 +22,8 @@ __all__ = ["SyntheticRolloutProblem"]
 
 
 class SyntheticRolloutProblem(Problem):
+    _NOT_CLONED = Problem._NOT_CLONED + ("_env_blob_state",)
+
     def __init__(
         self,
         *,
@@ -67,10 +69,49 @@ class SyntheticRolloutProblem(Problem):
     def _norm_mean_std(self):
         if self._obs_norm_enabled and self._obs_norm.has_data:
             return self._obs_norm.mean, self._obs_norm.stdev
+        return self._default_mean_std(self._device)
+
+    def _packed_env_blob(self, values: torch.Tensor) -> torch.Tensor:
+        """The rollout kernel's env blob with this generation's (mean, std)
+        in its tail. The blob is built once per device and lives as long as
+        the problem; each evaluation recomputes mean and stdev from the
+        running sums straight into its tail in ONE launch
+        (ops.obsnorm_pack_), so `obs_norm.update()` / `reset()` between
+        generations are seen. It is overwritten in place: the rollout that
+        reads it is queued on the same stream before the next pack, and
+        nothing else keeps a reference. Without the fused tail the blob is
+        concatenated anew from RunningNorm's properties."""
+        from .. import ops
+
+        spec = self._spec
+        tracked = self._obs_norm_enabled and self._obs_norm.has_data
+        device = values.device
+        if ops.fused_tail_for(values) is not None:
+            state = getattr(self, "_env_blob_state", None)
+            if state is None or state[0].device != device:
+                # a fresh blob carries the no-data defaults (mean 0, std 1)
+                state = [spec.env_blob(*self._default_mean_std(device), device=device), True]
+                self._env_blob_state = state
+            blob, holds_defaults = state
+            O = spec.obs_dim
+            if not tracked:
+                if not holds_defaults:
+                    blob[-2 * O : -O].zero_()
+                    blob[-O:].fill_(1.0)
+                    state[1] = True
+                return blob
+            rn = self._obs_norm
+            if ops.obsnorm_pack_(blob, blob.numel() - 2 * O, rn._count, rn._sum, rn._sum_sq, rn.min_variance):
+                state[1] = False
+                return blob
+        mean, std = self._norm_mean_std()
+        return spec.env_blob(mean, std, device=device)
+
+    def _default_mean_std(self, device):
         O = self._spec.obs_dim
         return (
-            torch.zeros(O, dtype=torch.float32, device=self._device),
-            torch.ones(O, dtype=torch.float32, device=self._device),
+            torch.zeros(O, dtype=torch.float32, device=device),
+            torch.ones(O, dtype=torch.float32, device=device),
         )
 
     def observation_normalization_data(self):
@@ -107,8 +148,7 @@ class SyntheticRolloutProblem(Problem):
             from .. import ops
 
             mod = ops.hip_required()
-            mean, std = self._norm_mean_std()
-            blob = spec.env_blob(mean, std, device=values.device)
+            blob = self._packed_env_blob(values)
             obs_stats = torch.zeros(2 * spec.obs_dim, dtype=torch.float32, device=values.device)
             if seed_buf is not None:
                 mod.bump_seed(seed_buf)  # fresh episode seed per replay, on device

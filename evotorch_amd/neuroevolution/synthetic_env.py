@@ -77,9 +77,13 @@ class SyntheticEnvSpec:
         return self.act_dim * self.obs_dim + self.act_dim
 
     def env_blob(self, mean: torch.Tensor, std: torch.Tensor, device=None) -> torch.Tensor:
-        """Pack (V, U_T, D2_T, c, wr, mean, std) contiguously as fp32. The
-        static matrices are cached per device; only mean/std change per
-        generation."""
+        """Pack (V, U_T, D2_T, c, wr, mean, std) contiguously as fp32 into a
+        NEW tensor (the static matrices are cached per device). This is
+        the layout's definition and what tests and tools call.
+        `SyntheticRolloutProblem` calls it once per device and then
+        overwrites the (mean, std) tail of that blob in place every
+        generation (`ops.obsnorm_pack_`), so its blob is not a snapshot:
+        whoever needs one clones it."""
         device = torch.device(device or self.device)
         cache = getattr(self, "_matrix_cache", None)
         if cache is None or cache[0] != device:

@@ -11,7 +11,8 @@ Every hot op of the framework goes through this module. The contract:
 
 Kernel inventory (docs/kernels.md): K1 sample_gaussian / affine_from_noise,
 K2 fused_rank (routed from utils/ranking.py), K3 es_gradients /
-snes_gradients, K4 clipup_step / adam_step, K5 cma_update_c, K5b potrf_tile,
+snes_gradients, K4 clipup_step / adam_step, K4b gaussian_clipup_update, K12
+obsnorm_pack / obsnorm_merge, K5 cma_update_c, K5b potrf_tile,
 K7 pareto_ranks / domination_counts, K9 mapelites_assign (routed from
 algorithms/mapelites.py), K10+K11 rollout_linear (called from
 neuroevolution/synthetic.py).
@@ -41,6 +42,12 @@ __all__ = [
     "es_gradients",
     "snes_gradients",
     "clipup_step_",
+    "gaussian_clipup_update",
+    "obsnorm_merge_",
+    "obsnorm_pack_",
+    "unfused_generation_tail",
+    "fused_tail_for",
+    "GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH",
     "fused_adam_step_",
     "pareto_ranks",
     "domination_counts",
@@ -102,6 +109,31 @@ def eager_on_gpu():
             del os.environ[_EAGER_ENV]
         else:
             os.environ[_EAGER_ENV] = previous
+
+
+_fused_tail = [True]
+
+
+@contextlib.contextmanager
+def unfused_generation_tail():
+    """Run the generation tail (distribution update, obs-norm merge and
+    env-blob packing) through the chains of separate launches that the
+    fused ops replace. The chains are the fused ops' oracle: both give the
+    same bits."""
+    previous = _fused_tail[0]
+    _fused_tail[0] = False
+    try:
+        yield
+    finally:
+        _fused_tail[0] = previous
+
+
+def fused_tail_for(t: torch.Tensor):
+    """The extension when `t` is an fp32 ROCm tensor and the fused
+    generation tail is on, else None (the caller runs its chain)."""
+    if _fused_tail[0] and t.dtype == torch.float32:
+        return hip_for(t)
+    return None
 
 
 def _dense(like: torch.Tensor, *operands: torch.Tensor):
@@ -325,6 +357,115 @@ def clipup_step_(
     v32 = v32 * scale
     velocity.copy_(v32.to(velocity.dtype))
     return velocity
+
+
+GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH = 65536  # one block; kUpdateMaxLength of es_kernels.hip
+
+
+def gaussian_clipup_update(
+    mu: torch.Tensor,
+    sigma: torch.Tensor,
+    velocity: torch.Tensor,
+    mu_grad: torch.Tensor,
+    sigma_grad: torch.Tensor,
+    *,
+    step_size: float,
+    max_speed: float,
+    momentum: float = 0.9,
+    sigma_lr: float,
+    stdev_min: Optional[float] = None,
+    stdev_max: Optional[float] = None,
+    stdev_max_change: Optional[float] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The distribution update of a separable Gaussian under ClipUp:
+    `velocity` takes one ClipUp step along `mu_grad` in place (as
+    `clipup_step_`), and fresh ``(mu + velocity, sigma')`` are returned,
+    where ``sigma' = sigma + sigma_lr * sigma_grad`` held inside the scalar
+    stdev bounds exactly as `utils.modify_tensor` holds it.
+
+    fp32 ROCm vectors up to GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH elements take
+    ONE kernel launch; anything else runs the chain of launches below. Both
+    give the same bits. No host sync either way (hipGraph-capturable)."""
+    mod = fused_tail_for(mu)
+    if (
+        mod is not None
+        and mu.numel() <= GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH
+        and all(t.dtype == torch.float32 and t.device == mu.device for t in (sigma, velocity, mu_grad, sigma_grad))
+        and velocity.is_contiguous()
+    ):
+        new_mu, new_sigma = mod.gaussian_clipup_update(
+            *_dense(mu, mu, sigma),
+            velocity,
+            *_dense(mu, mu_grad, sigma_grad),
+            float(step_size),
+            float(momentum),
+            float(max_speed),
+            float(sigma_lr),
+            None if stdev_min is None else float(stdev_min),
+            None if stdev_max is None else float(stdev_max),
+            None if stdev_max_change is None else float(stdev_max_change),
+        )
+        return new_mu, new_sigma
+    from ..utils.misc import modify_tensor
+
+    clipup_step_(velocity, mu_grad, step_size=step_size, max_speed=max_speed, momentum=momentum)
+    new_mu = mu + velocity
+    new_sigma = torch.add(sigma, sigma_grad, alpha=float(sigma_lr))
+    if stdev_min is not None or stdev_max is not None or stdev_max_change is not None:
+        new_sigma = modify_tensor(sigma, new_sigma, lb=stdev_min, ub=stdev_max, max_change=stdev_max_change)
+    return new_mu, new_sigma
+
+
+# ============================================================================
+# K12 — observation-normalization statistics
+# ============================================================================
+
+
+def obsnorm_merge_(count: torch.Tensor, total: torch.Tensor, total_sq: torch.Tensor, c, s: torch.Tensor, ss: torch.Tensor):
+    """``count += c; total += s; total_sq += ss`` on RunningNorm's state.
+    `c` is a host number or a one-element tensor; a device tensor is read
+    on the device (no host sync). One launch on fp32 ROCm state."""
+    mod = fused_tail_for(total)
+    c_is_tensor = isinstance(c, torch.Tensor)
+    if (
+        mod is not None
+        and count.dtype == torch.float64
+        and count.device == total.device
+        and total_sq.dtype == torch.float32
+        and s.shape == total.shape
+        and ss.shape == total.shape
+        and total.is_contiguous()
+        and total_sq.is_contiguous()
+        and total.numel() > 0
+        and (not c_is_tensor or (c.device == total.device and c.numel() == 1 and c.dtype in (torch.float32, torch.float64)))
+    ):
+        mod.obsnorm_merge(count, total, total_sq, 0.0 if c_is_tensor else float(c), c if c_is_tensor else None, *_dense(total, s, ss))
+        return
+    if c_is_tensor:
+        count += c.to(count.device, torch.float64)
+    else:
+        count += float(c)
+    total += s
+    total_sq += ss
+
+
+def obsnorm_pack_(blob: torch.Tensor, offset: int, count: torch.Tensor, total: torch.Tensor, total_sq: torch.Tensor, min_variance: float) -> bool:
+    """Write RunningNorm's mean and stdev (fp32) into
+    ``blob[offset : offset + 2 * O]`` in one launch, straight from the
+    running sums. Returns False, having done nothing, where the fused path
+    does not apply (the caller then goes through RunningNorm's properties)."""
+    mod = fused_tail_for(blob)
+    if (
+        mod is None
+        or count.dtype != torch.float64
+        or total.dtype != torch.float32
+        or total_sq.dtype != torch.float32
+        or not (count.device == total.device == total_sq.device == blob.device)
+        or not (blob.is_contiguous() and total.is_contiguous() and total_sq.is_contiguous())
+    ):
+        return False
+    mod.obsnorm_pack(count, total, total_sq, float(min_variance), blob, int(offset))
+    return True
 
 
 def fused_adam_step_(

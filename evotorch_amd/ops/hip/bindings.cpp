@@ -11,6 +11,16 @@ std::vector<torch::Tensor> es_gradients(torch::Tensor samples, torch::Tensor mu,
 std::vector<torch::Tensor> snes_gradients(torch::Tensor samples, torch::Tensor mu, torch::Tensor sigma,
                                           torch::Tensor weights);
 void clipup_step(torch::Tensor velocity, torch::Tensor grad, double step_size, double max_speed, double momentum);
+std::vector<torch::Tensor> gaussian_clipup_update(torch::Tensor mu, torch::Tensor sigma, torch::Tensor velocity,
+                                                  torch::Tensor mu_grad, torch::Tensor sigma_grad, double step_size,
+                                                  double momentum, double max_speed, double sigma_lr,
+                                                  c10::optional<double> stdev_min, c10::optional<double> stdev_max,
+                                                  c10::optional<double> stdev_max_change);
+int64_t gaussian_clipup_update_max_length();
+void obsnorm_pack(torch::Tensor count, torch::Tensor sum, torch::Tensor sumsq, double min_variance,
+                  torch::Tensor blob, int64_t offset);
+void obsnorm_merge(torch::Tensor count, torch::Tensor sum, torch::Tensor sumsq, double c_host,
+                   c10::optional<torch::Tensor> c_device, torch::Tensor s, torch::Tensor ss);
 void adam_step(torch::Tensor step_out, torch::Tensor grad, torch::Tensor m, torch::Tensor v, int64_t step_count,
                double stepsize, double beta1, double beta2, double epsilon);
 void adam_step_graphsafe(torch::Tensor step_out, torch::Tensor grad, torch::Tensor m, torch::Tensor v,
@@ -41,6 +51,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("es_gradients", &ea::es_gradients, "K3: fused (mu, sigma) ES gradient reduction");
     m.def("snes_gradients", &ea::snes_gradients, "K3: SNES raw-noise gradient reduction");
     m.def("clipup_step", &ea::clipup_step, "K4: fused ClipUp velocity update (no host sync)");
+    m.def("gaussian_clipup_update", &ea::gaussian_clipup_update,
+          "K4b: ClipUp step, mu + velocity and the bounded sigma step in one launch; returns (new_mu, new_sigma)",
+          py::arg("mu"), py::arg("sigma"), py::arg("velocity"), py::arg("mu_grad"), py::arg("sigma_grad"),
+          py::arg("step_size"), py::arg("momentum"), py::arg("max_speed"), py::arg("sigma_lr"),
+          py::arg("stdev_min") = c10::optional<double>(), py::arg("stdev_max") = c10::optional<double>(),
+          py::arg("stdev_max_change") = c10::optional<double>());
+    m.def("gaussian_clipup_update_max_length", &ea::gaussian_clipup_update_max_length,
+          "largest solution length gaussian_clipup_update accepts");
+    m.def("obsnorm_pack", &ea::obsnorm_pack,
+          "K12: obs-norm mean/stdev from (count, sum, sumsq), written into blob[offset : offset + 2*O]");
+    m.def("obsnorm_merge", &ea::obsnorm_merge,
+          "K12: count += c; sum += s; sumsq += ss in one launch (c: host value, or a 0-dim device tensor)");
     m.def("adam_step", &ea::adam_step, "K4: fused Adam ascent step");
     m.def("adam_step_graphsafe", &ea::adam_step_graphsafe,
           "K4 (hipGraph-safe): Adam with device-side step counter");

@@ -13,7 +13,9 @@
 //   fp32 partials — the fused kernel produces BOTH mu_grad and sigma_grad
 //   from the single pass over X, halving traffic vs two library GEMVs.
 // * ClipUp is three tiny kernels chained on the stream (norm, update+norm,
-//   scale) — no host synchronization anywhere.
+//   scale) — no host synchronization anywhere. PGPE's whole update (ClipUp,
+//   mu + velocity, bounded sigma step) also exists as ONE single-block
+//   kernel with the same bits (gaussian_clipup_update).
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -386,6 +388,136 @@ void clipup_step(torch::Tensor velocity, torch::Tensor grad, double step_size, d
     });
 }
 
+// ---------------------------------------------------------------------------
+// K4b: the whole distribution update of a separable Gaussian under ClipUp
+// in ONE launch of one block: clipup_step on velocity, new_mu = mu +
+// velocity, new_sigma = sigma + lr·sigma_grad held inside the stdev bounds
+// (utils/misc.py modify_tensor with scalar bounds). Every value is what the
+// chain of launches gives, bit for bit: elementwise steps are rounded one by
+// one as separate kernels round them (contraction off; fmaf only where the
+// chain has one), and the two norms are summed in clipup_step's own tree.
+// ---------------------------------------------------------------------------
+
+constexpr int kUpdateThreads = 1024;
+// 256 virtual blocks of 256 threads: below grid_for's cap of 1024 blocks, so
+// every virtual thread of clipup_step's kernels holds exactly one element
+constexpr int64_t kUpdateMaxLength = 65536;
+
+// Σ value(i)² over [0, n) in the order of sumsq_kernel / clipup_update_kernel
+// followed by reduce_partials_kernel: virtual blocks of 256 threads, one
+// element each, reduced by block_reduce_sum (four wave sums s0..s3 of a
+// block combine as (s0 + s2) + (s1 + s3): lane 0 of a shfl_down tree over
+// s0 s1 s2 s3 0 0 ..), then the partials, one per thread of a 256-thread
+// block, by the same reduction. The 16 waves of this block walk the virtual
+// blocks four at a time. `value` is called once for every i < n.
+// wave_sums: [1024], tops: [4]; the result is returned to all threads.
+template <typename F>
+__device__ __forceinline__ float clipup_tree_sumsq(F value, int n, float* wave_sums, float* tops) {
+    const int tid = threadIdx.x, lane = tid & (kWaveSize - 1), wave = tid / kWaveSize;
+    const int vblocks = (n + 255) / 256;
+    for (int base = 0; base < vblocks * 256; base += kUpdateThreads) {
+        const int i = base + tid;
+        const float x = (i < n) ? value(i) : 0.0f;
+        const float w = wave_reduce_sum(fmaf(x, x, 0.0f));
+        if (lane == 0) wave_sums[base / kWaveSize + wave] = w;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        float part = 0.0f;
+        if (tid < vblocks)
+            part = (wave_sums[4 * tid] + wave_sums[4 * tid + 2]) + (wave_sums[4 * tid + 1] + wave_sums[4 * tid + 3]);
+        part = wave_reduce_sum(part);
+        if (lane == 0) tops[wave] = part;
+    }
+    __syncthreads();
+    return (tops[0] + tops[2]) + (tops[1] + tops[3]);
+}
+
+// torch.maximum / torch.minimum: a NaN of either side comes through
+__device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
+__device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : fminf(a, b)); }
+
+constexpr int kHasStdevMin = 1, kHasStdevMax = 2, kHasStdevMaxChange = 4;
+
+__global__ __launch_bounds__(kUpdateThreads) void gaussian_clipup_update_kernel(
+    const float* __restrict__ mu, const float* __restrict__ sigma, float* __restrict__ velocity,
+    const float* __restrict__ mu_grad, const float* __restrict__ sigma_grad, float* __restrict__ new_mu,
+    float* __restrict__ new_sigma, int n, float step_size, float momentum, float max_speed, float sigma_lr,
+    float stdev_min, float stdev_max, float stdev_max_change, int bounds) {
+#pragma clang fp contract(off)
+    __shared__ float wave_sums[kUpdateThreads];
+    __shared__ float tops[4];
+
+    const float gnorm_sq = clipup_tree_sumsq([&](int i) { return mu_grad[i]; }, n, wave_sums, tops);
+    const float gnorm = sqrtf(fmaxf(gnorm_sq, 1e-30f));
+    const float scale = step_size / gnorm;
+    const float vnorm_sq = clipup_tree_sumsq(
+        [&](int i) {
+            const float v = fmaf(momentum, velocity[i], mu_grad[i] * scale);
+            velocity[i] = v;
+            return v;
+        },
+        n, wave_sums, tops);
+    const float vnorm = sqrtf(fmaxf(vnorm_sq, 1e-30f));
+    const float clip = fminf(max_speed / vnorm, 1.0f);
+
+    // element i was written above by this same thread
+    for (int i = threadIdx.x; i < n; i += kUpdateThreads) {
+        float v = velocity[i];
+        if (!(clip >= 1.0f)) {
+            v = v * clip;
+            velocity[i] = v;
+        }
+        new_mu[i] = mu[i] + v;
+
+        const float s = sigma[i];
+        // torch.add(sigma, grad, alpha=lr) is one fma in torch's ROCm build
+        float target = fmaf(sigma_lr, sigma_grad[i], s);
+        if (bounds & kHasStdevMaxChange) {
+            const float allowed = fabsf(s) * stdev_max_change;
+            float lo = s - allowed;
+            float hi = allowed + s;
+            if ((bounds & kHasStdevMin) && lo == lo) lo = fmaxf(lo, stdev_min);
+            if ((bounds & kHasStdevMax) && hi == hi) hi = fminf(hi, stdev_max);
+            target = nan_min(nan_max(target, lo), hi);
+        } else if (target == target) {
+            if (bounds & kHasStdevMin) target = fmaxf(target, stdev_min);
+            if (bounds & kHasStdevMax) target = fminf(target, stdev_max);
+        }
+        new_sigma[i] = target;
+    }
+}
+
+std::vector<torch::Tensor> gaussian_clipup_update(torch::Tensor mu, torch::Tensor sigma, torch::Tensor velocity,
+                                                  torch::Tensor mu_grad, torch::Tensor sigma_grad, double step_size,
+                                                  double momentum, double max_speed, double sigma_lr,
+                                                  c10::optional<double> stdev_min, c10::optional<double> stdev_max,
+                                                  c10::optional<double> stdev_max_change) {
+    check_primary(mu, "mu", 1);
+    TORCH_CHECK(mu.scalar_type() == torch::kFloat32, "gaussian_clipup_update expects float32, got ", mu.scalar_type());
+    const int64_t n = mu.numel();
+    TORCH_CHECK(n >= 1 && n <= kUpdateMaxLength, "gaussian_clipup_update supports 1 <= L <= ", kUpdateMaxLength,
+                ", got ", n);
+    check_operand(sigma, "sigma", mu, n);
+    check_operand(velocity, "velocity", mu, n);
+    check_operand(mu_grad, "mu_grad", mu, n);
+    check_operand(sigma_grad, "sigma_grad", mu, n);
+    auto new_mu = torch::empty_like(mu);
+    auto new_sigma = torch::empty_like(sigma);
+    const int bounds = (stdev_min ? kHasStdevMin : 0) | (stdev_max ? kHasStdevMax : 0) |
+                       (stdev_max_change ? kHasStdevMaxChange : 0);
+    auto stream = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL(gaussian_clipup_update_kernel, dim3(1), dim3(kUpdateThreads), 0, stream, mu.data_ptr<float>(),
+                       sigma.data_ptr<float>(), velocity.data_ptr<float>(), mu_grad.data_ptr<float>(),
+                       sigma_grad.data_ptr<float>(), new_mu.data_ptr<float>(), new_sigma.data_ptr<float>(), (int)n,
+                       (float)step_size, (float)momentum, (float)max_speed, (float)sigma_lr,
+                       (float)stdev_min.value_or(0.0), (float)stdev_max.value_or(0.0),
+                       (float)stdev_max_change.value_or(0.0), bounds);
+    return {new_mu, new_sigma};
+}
+
+int64_t gaussian_clipup_update_max_length() { return kUpdateMaxLength; }
+
 // One element of the Adam ascent step, shared by both kernels below.
 template <typename T>
 __device__ __forceinline__ void adam_element(T* __restrict__ step_out, const T* __restrict__ grad, T* __restrict__ m,
@@ -470,46 +602,139 @@ void adam_step(torch::Tensor step_out, torch::Tensor grad, torch::Tensor m, torc
 // K2: fused fitness ranking -> utility map (reference
 // tools/ranking.py:24-216). One launch replaces the torch chain
 // (rocPRIM radix sort + scatter + 3-4 elementwise maps): a single-block
-// bitonic sort over LDS (N <= 8192 padded to a power of two) followed by
+// bitonic sort (N <= 8192 padded to a power of two p with +inf) followed by
 // the utility map written back through the sorted index payload.
 // method: 0 = centered (rank/(n-1) - 0.5), 1 = linear (rank/(n-1)),
 //         2 = nes (log-utilities, normalized to sum to ~0).
+//
+// The comparator network is the serial one — for k = 2, 4 .. p, for
+// j = k/2 .. 1: compare-exchange (i, i^j), ascending where (i & k) == 0 —
+// and ties stay where the network leaves them, so its step order and swap
+// predicate fix the result bit for bit. Only the place of the data varies:
+// thread t of the 1024 holds positions [t·E, (t+1)·E), E = max(1, p/1024),
+// as (key, index) pairs in registers. A step with j < E exchanges inside a
+// thread, one with E <= j < 64·E between two lanes of a wave (no barrier),
+// and only j >= 64·E goes through LDS behind barriers: 10 of the 78 steps at
+// p = 4096. In the two-thread forms both threads evaluate the predicate of
+// the lower position on the same two keys and so agree.
 // ---------------------------------------------------------------------------
 
-__global__ __launch_bounds__(1024) void fused_rank_kernel(const float* __restrict__ fit, float* __restrict__ out,
-                                                          int n, int p, int method, bool higher_better) {
+constexpr int kRankThreads = 1024;
+
+// The swap predicate on fp32 keys a (lower position) and b, NaN-robust:
+// NaNs order last so they rank as best-key (matches torch argsort's
+// NaN-is-largest behavior), and on a tie nothing moves:
+//   ascending:  b < a || (isnan(a) && !isnan(b))
+//   descending: a < b || (isnan(b) && !isnan(a))
+// It is evaluated on order keys: rank_order_key maps fp32 to int32 such that
+// the ascending predicate is exactly key(b) < key(a) and the descending one
+// key(a) < key(b) — monotone on the non-NaN values, -0 and +0 onto one key
+// (neither is < the other), every NaN onto INT_MAX (above +inf's key, and
+// no NaN before another). One integer compare then decides a
+// compare-exchange; on one CU the predicate's ~20 float instructions per
+// evaluation were most of the kernel's time.
+__device__ __forceinline__ int rank_order_key(float x) {
+    if (isnan(x)) return INT_MAX;
+    const int bits = __float_as_int(x);
+    return bits >= 0 ? bits : -(bits & 0x7fffffff);
+}
+
+// This thread's side of the compare-exchange with the position held by a
+// partner thread. `lower_is_up` = (this thread holds the lower position) ==
+// (the pair sorts ascending): then it takes the partner's pair iff the
+// partner's key is smaller, otherwise iff it is larger.
+__device__ __forceinline__ void rank_exchange(int& key, int& idx, int other_key, int other_idx, bool lower_is_up) {
+    if (lower_is_up ? (other_key < key) : (key < other_key)) {
+        key = other_key;
+        idx = other_idx;
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(kRankThreads) void fused_rank_kernel(const float* __restrict__ fit,
+                                                                  float* __restrict__ out, int n, int p, int method,
+                                                                  bool higher_better) {
     extern __shared__ unsigned char rank_lds[];
+    constexpr int kSlots = E * kRankThreads;  // >= p
     float* keys = reinterpret_cast<float*>(rank_lds);
-    int* idx = reinterpret_cast<int*>(keys + p);
-    float* scratch = reinterpret_cast<float*>(idx + p);  // [32] for the nes sum
+    int* idx = reinterpret_cast<int*>(keys + kSlots);
+    float* scratch = reinterpret_cast<float*>(idx + kSlots);  // [32] for the nes sum
+    int* order_keys = reinterpret_cast<int*>(keys);           // the sort's use of the key slots
 
     const int tid = threadIdx.x;
-    for (int i = tid; i < p; i += blockDim.x) {
-        keys[i] = (i < n) ? (higher_better ? fit[i] : -fit[i]) : INFINITY;
-        idx[i] = i;
+    int key[E];
+    int id[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = tid * E + e;
+        key[e] = rank_order_key((i < n) ? (higher_better ? fit[i] : -fit[i]) : INFINITY);
+        id[e] = i;
     }
-    __syncthreads();
     // bitonic sort ascending: position 0 = worst
     for (int k = 2; k <= p; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < p; i += blockDim.x) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool up = (i & k) == 0;
-                    const float a = keys[i], b = keys[ixj];
-                    // NaN-robust: order NaNs last so they rank as best-key
-                    // (matches torch argsort's NaN-is-largest behavior)
-                    const bool swap = up ? (b < a || (isnan(a) && !isnan(b)))
-                                         : (a < b || (isnan(b) && !isnan(a)));
-                    if (swap) {
-                        keys[i] = b; keys[ixj] = a;
-                        const int t = idx[i]; idx[i] = idx[ixj]; idx[ixj] = t;
+        int j = k >> 1;
+        // with a partner in another thread j >= E, so k > E and the
+        // direction bit (i & k) is the same for all E positions of a thread
+        const bool up = ((tid * E) & k) == 0;
+        // partner in another wave: through LDS, laid out [e][thread] so
+        // that lanes touch consecutive banks
+        for (; j >= 64 * E; j >>= 1) {
+            const int m = j / E;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                order_keys[e * kRankThreads + tid] = key[e];
+                idx[e * kRankThreads + tid] = id[e];
+            }
+            __syncthreads();
+            int other_key[E];
+            int other_id[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                other_key[e] = order_keys[e * kRankThreads + (tid ^ m)];
+                other_id[e] = idx[e * kRankThreads + (tid ^ m)];
+            }
+            __syncthreads();
+            const bool lower_is_up = ((tid & m) == 0) == up;
+#pragma unroll
+            for (int e = 0; e < E; ++e) rank_exchange(key[e], id[e], other_key[e], other_id[e], lower_is_up);
+        }
+        // partner in another lane of this wave
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            if (m * E < k) {
+                const bool lower_is_up = ((tid & m) == 0) == up;
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const int other_key = __shfl_xor(key[e], m, 64);
+                    const int other_id = __shfl_xor(id[e], m, 64);
+                    rank_exchange(key[e], id[e], other_key, other_id, lower_is_up);
+                }
+            }
+        }
+        // partner in this thread
+#pragma unroll
+        for (int jj = E / 2; jj > 0; jj >>= 1) {
+            if (jj < k) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    if ((e & jj) == 0) {
+                        const int a = key[e], b = key[e | jj];
+                        if ((((tid * E + e) & k) == 0) ? (b < a) : (a < b)) {
+                            key[e] = b; key[e | jj] = a;
+                            const int t = id[e]; id[e] = id[e | jj]; id[e | jj] = t;
+                        }
                     }
                 }
             }
-            __syncthreads();
         }
     }
+    // the sorted index payload back to LDS in position order for the utility
+    // map (the map reads no key; nes reuses the key slots for its utilities)
+#pragma unroll
+    for (int e = 0; e < E; ++e) idx[tid * E + e] = id[e];
+    __syncthreads();
+    // a pad slot (index >= n) can sort in front of real ones only for
+    // non-finite fitness; it has no output element
     if (method == 2) {
         // NES log-utilities need their global sum before the final map
         float partial = 0.0f;
@@ -533,14 +758,29 @@ __global__ __launch_bounds__(1024) void fused_rank_kernel(const float* __restric
         __syncthreads();
         const float denom = scratch[0];
         const float inv_n = 1.0f / (float)n;
-        for (int i = tid; i < n; i += blockDim.x) out[idx[i]] = keys[i] / denom - inv_n;
+        for (int i = tid; i < n; i += blockDim.x)
+            if (idx[i] < n) out[idx[i]] = keys[i] / denom - inv_n;
         return;
     }
     const float inv = (n > 1) ? 1.0f / (float)(n - 1) : 0.0f;
     for (int i = tid; i < n; i += blockDim.x) {
         const float r = (float)i;
-        out[idx[i]] = (method == 0) ? (r * inv - 0.5f) : (r * inv);
+        if (idx[i] < n) out[idx[i]] = (method == 0) ? (r * inv - 0.5f) : (r * inv);
     }
+}
+
+template <int E>
+static void fused_rank_launch(const torch::Tensor& fit, torch::Tensor& out, int n, int p, int method,
+                              bool higher_better) {
+    constexpr size_t lds = (size_t)E * kRankThreads * 8 + 32 * 4;
+    static bool attr_set = false;
+    if (!attr_set && lds > 64 * 1024) {
+        allow_max_dynamic_lds(reinterpret_cast<const void*>(&fused_rank_kernel<E>));
+        attr_set = true;
+    }
+    auto stream = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL((fused_rank_kernel<E>), dim3(1), dim3(kRankThreads), lds, stream, fit.data_ptr<float>(),
+                       out.data_ptr<float>(), n, p, method, higher_better);
 }
 
 torch::Tensor fused_rank(torch::Tensor fitnesses, int64_t method, bool higher_better) {
@@ -551,10 +791,12 @@ torch::Tensor fused_rank(torch::Tensor fitnesses, int64_t method, bool higher_be
     int p = 1;
     while (p < n) p <<= 1;
     auto out = torch::empty({n}, fit.options());
-    const size_t lds = (size_t)p * 8 + 32 * 4;
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(fused_rank_kernel, dim3(1), dim3(1024), lds, stream, fit.data_ptr<float>(),
-                       out.data_ptr<float>(), n, p, (int)method, higher_better);
+    switch (std::max(1, p / kRankThreads)) {
+        case 1: fused_rank_launch<1>(fit, out, n, p, (int)method, higher_better); break;
+        case 2: fused_rank_launch<2>(fit, out, n, p, (int)method, higher_better); break;
+        case 4: fused_rank_launch<4>(fit, out, n, p, (int)method, higher_better); break;
+        default: fused_rank_launch<8>(fit, out, n, p, (int)method, higher_better); break;
+    }
     return out;
 }
 

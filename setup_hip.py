@@ -24,6 +24,7 @@ setup(
             sources=[
                 os.path.join(SRC, "bindings.cpp"),
                 os.path.join(SRC, "es_kernels.hip"),
+                os.path.join(SRC, "obsnorm.hip"),
                 os.path.join(SRC, "rollout.hip"),
                 os.path.join(SRC, "rollout_v7.hip"),
                 os.path.join(SRC, "rollout_m7.hip"),
