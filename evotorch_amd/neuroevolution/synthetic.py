@@ -51,8 +51,15 @@ class SyntheticRolloutProblem(Problem):
         self._decrease_rewards_by = float(decrease_rewards_by)
         self._pending_stats = None
         self._graph_seed_buf: Optional[torch.Tensor] = None  # device seed chain, set by enable_graph_mode
-        self.last_eval_interaction_count = 0
+        self._last_interactions = 0
         self._total_interactions = 0
+        # Terminating rollouts on the GPU count their interactions on the
+        # device, in place in this persistent int64 pair (last evaluation,
+        # total), so that replays of a captured generation keep counting.
+        # They become host integers only when read.
+        self._device_interactions: Optional[torch.Tensor] = None
+        self._last_interactions_on_device = False
+        self._last_episode_lengths = None  # tensor, or (n, device) after fixed-length episodes
         self._episode_count = 0
         self.after_eval_hook.append(self._after_eval_status_getter)
 
@@ -65,6 +72,40 @@ class SyntheticRolloutProblem(Problem):
     @property
     def obs_norm(self) -> RunningNorm:
         return self._obs_norm
+
+    @property
+    def last_episode_lengths(self) -> Optional[torch.Tensor]:
+        """Steps each member of the last evaluated batch ran, as int32 of
+        shape [n] on the problem's device; None before the first
+        evaluation."""
+        lengths = self._last_episode_lengths
+        if isinstance(lengths, tuple):  # fixed-length episodes
+            n, device = lengths
+            lengths = torch.full((n,), self._spec.episode_length, dtype=torch.int32, device=device)
+            self._last_episode_lengths = lengths
+        return lengths
+
+    @property
+    def last_eval_interaction_count(self) -> int:
+        """Environment steps of the last evaluation. After a terminating
+        rollout on the GPU, reading this synchronises with the device."""
+        if self._last_interactions_on_device:
+            return int(self._device_interactions[0])
+        return self._last_interactions
+
+    @last_eval_interaction_count.setter
+    def last_eval_interaction_count(self, value: int):
+        self._last_interactions = int(value)
+        self._last_interactions_on_device = False
+
+    @property
+    def total_interaction_count(self) -> int:
+        """Environment steps of all evaluations so far (one device read
+        when terminating rollouts ran on the GPU)."""
+        total = self._total_interactions
+        if self._device_interactions is not None:
+            total += int(self._device_interactions[1])
+        return total
 
     def _norm_mean_std(self):
         if self._obs_norm_enabled and self._obs_norm.has_data:
@@ -152,39 +193,95 @@ class SyntheticRolloutProblem(Problem):
             obs_stats = torch.zeros(2 * spec.obs_dim, dtype=torch.float32, device=values.device)
             if seed_buf is not None:
                 mod.bump_seed(seed_buf)  # fresh episode seed per replay, on device
-            fitness = mod.rollout_linear(
-                values.contiguous(),
-                blob,
-                obs_stats,
-                spec.obs_dim,
-                spec.act_dim,
-                spec.rank,
-                spec.episode_length,
-                spec.alive_bonus,
-                spec.act_cost,
-                init_seed,
-                member_offset,
-                spec.policy_hidden,
-                seed_buf,
-            )
-            triple = (float(n) * spec.episode_length, obs_stats[: spec.obs_dim], obs_stats[spec.obs_dim :])
+            if spec.terminates:
+                lengths = torch.empty(n, dtype=torch.int32, device=values.device)
+                fitness = mod.rollout_terminating(
+                    values.contiguous(),
+                    blob,
+                    obs_stats,
+                    lengths,
+                    spec.obs_dim,
+                    spec.act_dim,
+                    spec.rank,
+                    spec.episode_length,
+                    spec.alive_bonus,
+                    spec.act_cost,
+                    init_seed,
+                    member_offset,
+                    spec.policy_hidden,
+                    spec.health_index,
+                    spec.healthy_range[0],
+                    spec.healthy_range[1],
+                    seed_buf,
+                )
+                count = lengths.sum()  # stays on the device: no host sync, capturable
+            else:
+                fitness = mod.rollout_linear(
+                    values.contiguous(),
+                    blob,
+                    obs_stats,
+                    spec.obs_dim,
+                    spec.act_dim,
+                    spec.rank,
+                    spec.episode_length,
+                    spec.alive_bonus,
+                    spec.act_cost,
+                    init_seed,
+                    member_offset,
+                    spec.policy_hidden,
+                    seed_buf,
+                )
+                lengths = None
+                count = float(n) * spec.episode_length
+            triple = (count, obs_stats[: spec.obs_dim], obs_stats[spec.obs_dim :])
         else:
             mean, std = self._norm_mean_std()
-            fitness, triple = rollout_eager(
-                spec, values.to(torch.float32), mean, std, init_seed=init_seed, member_offset=member_offset
+            fitness, triple, lengths = rollout_eager(
+                spec,
+                values.to(torch.float32),
+                mean,
+                std,
+                init_seed=init_seed,
+                member_offset=member_offset,
+                return_steps=True,
             )
+            lengths = lengths.to(torch.int32) if spec.terminates else None
         if self._decrease_rewards_by != 0.0:
-            fitness = fitness - self._decrease_rewards_by * spec.episode_length
+            # per step survived
+            survived = spec.episode_length if lengths is None else lengths.to(fitness.dtype)
+            fitness = fitness - self._decrease_rewards_by * survived
         batch.set_evals(fitness.to(self._eval_dtype))
+        if lengths is None:
+            self._last_episode_lengths = (n, values.device)  # all episode_length: built when read
+            self.last_eval_interaction_count = n * spec.episode_length
+            self._total_interactions += n * spec.episode_length
+        elif lengths.device.type == "cuda":
+            self._last_episode_lengths = lengths
+            counters = self._device_interactions
+            if counters is None or counters.device != lengths.device:
+                carried = 0 if counters is None else int(counters[1])
+                counters = torch.tensor([0, carried], dtype=torch.int64, device=lengths.device)
+                self._device_interactions = counters
+            counters[0].copy_(triple[0])
+            counters[1].add_(triple[0])
+            self._last_interactions_on_device = True
+            # the count RunningNorm's merge kernel reads on the device
+            triple = (triple[0].to(torch.float64).reshape(1), triple[1], triple[2])
+        else:
+            self._last_episode_lengths = lengths
+            self.last_eval_interaction_count = int(triple[0])
+            self._total_interactions += int(triple[0])
         self._pending_stats = triple
-        self.last_eval_interaction_count = n * spec.episode_length
-        self._total_interactions += n * spec.episode_length
         self._episode_count += n
 
     def _after_eval_status_getter(self, batch) -> dict:
         self._merge_pending_stats()
+        total = self._total_interactions
+        if self._device_interactions is not None:
+            # a 0-dim device tensor, like `mean_eval`: no host sync here
+            total = self._device_interactions[1] + total
         return {
-            "total_interaction_count": self._total_interactions,
+            "total_interaction_count": total,
             "total_episode_count": self._episode_count,
         }
 
@@ -201,7 +298,11 @@ class SyntheticRolloutProblem(Problem):
         self._pending_stats = None
         comm = self._comm
         if comm is not None and comm.world_size > 1:
-            packed = torch.cat([torch.tensor([count], dtype=torch.float32, device=s.device), s.reshape(-1), ss.reshape(-1)])
+            if isinstance(count, torch.Tensor):  # a device count stays there: no .item()
+                head = count.reshape(1).to(s.device, torch.float32)
+            else:
+                head = torch.tensor([count], dtype=torch.float32, device=s.device)
+            packed = torch.cat([head, s.reshape(-1), ss.reshape(-1)])
             O = self._spec.obs_dim
 
             def merge(reduced: torch.Tensor):

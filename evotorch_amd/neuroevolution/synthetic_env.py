@@ -11,6 +11,11 @@ low-rank neural dynamics:
     r   = wr·o' + alive_bonus − act_cost·‖a‖²/A
     o₀  = 0.1·N(0, I)  (philox-deterministic per global member index)
 
+With `healthy_range=(lo, hi)` an episode also ends early, as Humanoid's
+does when the torso height (its obs[0]) leaves the healthy range: a member
+is done after the step whose bf16(o'[health_index]) is outside [lo, hi]
+(a NaN is outside), and contributes nothing afterwards.
+
 (Green-field MI355X substitute for the reference's brax/gym env plumbing,
 /root/reference/src/evotorch/neuroevolution/net/vecrl.py:616-1664 — the
 rollout CONTRACT matches VecGymNE's batched env, the dynamics are
@@ -49,6 +54,8 @@ class SyntheticEnvSpec:
         act_cost: float = 0.05,
         env_seed: int = 1234,
         policy_hidden: int = 0,   # 0 = linear policy; H = one tanh hidden layer
+        healthy_range: Optional[Tuple[float, float]] = None,   # None = fixed-length episodes
+        health_index: int = 0,
         device="cpu",
     ):
         self.obs_dim = int(obs_dim)
@@ -59,6 +66,15 @@ class SyntheticEnvSpec:
         self.alive_bonus = float(alive_bonus)
         self.act_cost = float(act_cost)
         self.env_seed = int(env_seed)
+        self.health_index = int(health_index)
+        if not 0 <= self.health_index < self.obs_dim:
+            raise ValueError(f"health_index must be in [0, {self.obs_dim}), got {health_index}")
+        if healthy_range is not None:
+            lo, hi = (float(v) for v in healthy_range)
+            if not lo <= hi:  # also true of a NaN bound
+                raise ValueError(f"healthy_range must satisfy lo <= hi, got ({lo}, {hi})")
+            healthy_range = (lo, hi)
+        self.healthy_range = healthy_range
         g = torch.Generator().manual_seed(self.env_seed)
         O, A, R = self.obs_dim, self.act_dim, self.rank
         # mildly contractive dynamics so rollouts neither explode nor die
@@ -68,6 +84,11 @@ class SyntheticEnvSpec:
         self.c = torch.randn(O, generator=g) * 0.05
         self.wr = torch.randn(O, generator=g) * (1.0 / O**0.5)
         self.device = torch.device(device)
+
+    @property
+    def terminates(self) -> bool:
+        """Whether episodes can end before `episode_length`."""
+        return self.healthy_range is not None
 
     @property
     def solution_length(self) -> int:
@@ -124,12 +145,19 @@ def rollout_eager(
     init_seed: int = 0,
     member_offset: int = 0,
     bf16_operands: bool = True,
+    return_steps: bool = False,
 ) -> Tuple[torch.Tensor, Tuple[float, torch.Tensor, torch.Tensor]]:
     """Eager (device-agnostic) reference of the fused rollout kernel.
 
-    Returns (fitness[N], (count, obs_sum[O], obs_sumsq[O])).
+    Returns (fitness[N], (count, obs_sum[O], obs_sumsq[O])), followed by
+    the int64 episode lengths [N] when `return_steps` is true.
     With bf16_operands=True the matrices are quantized to bf16 before the
-    fp32-accumulated products, mirroring the kernel's LDS storage."""
+    fp32-accumulated products, mirroring the kernel's LDS storage.
+
+    With `spec.healthy_range` set, a member is done after the step whose
+    bf16 o'[spec.health_index] is outside the range; done members are
+    masked out with `torch.where`, so what an alive member computes per
+    step is unchanged. The count is then the sum of the lengths."""
     steps = spec.episode_length if steps is None else int(steps)
     N = params.shape[0]
     O, A, R = spec.obs_dim, spec.act_dim, spec.rank
@@ -163,6 +191,10 @@ def rollout_eager(
     fitness = torch.zeros(N, dtype=dt, device=device)
     obs_sum = torch.zeros(O, dtype=dt, device=device)
     obs_sumsq = torch.zeros(O, dtype=dt, device=device)
+    terminates = spec.terminates
+    alive = torch.ones(N, dtype=torch.bool, device=device)
+    lengths = torch.zeros(N, dtype=torch.int64, device=device)
+    zero = torch.zeros((), dtype=dt, device=device)
     for _ in range(steps):
         obs_n = q((obs - mean_f) * inv_std)
         if H > 0:
@@ -174,8 +206,26 @@ def rollout_eager(
         act_b = q(act)
         h = q(obs @ V.T)  # (N, R)
         o_new = torch.tanh(h @ U_T + act_b @ D2_T + c)
-        fitness = fitness + o_new @ wr + spec.alive_bonus - act_cost_term
-        obs_sum += o_new.sum(0)
-        obs_sumsq += (o_new**2).sum(0)
-        obs = q(o_new)
-    return fitness, (float(N * steps), obs_sum, obs_sumsq)
+        if not terminates:
+            fitness = fitness + o_new @ wr + spec.alive_bonus - act_cost_term
+            obs_sum += o_new.sum(0)
+            obs_sumsq += (o_new**2).sum(0)
+            obs = q(o_new)
+            continue
+        fitness = torch.where(alive, fitness + o_new @ wr + spec.alive_bonus - act_cost_term, fitness)
+        counted = torch.where(alive[:, None], o_new, zero)
+        obs_sum += counted.sum(0)
+        obs_sumsq += (counted**2).sum(0)
+        lengths += alive
+        # a done member's observation stays where it ended
+        obs = torch.where(alive[:, None], q(o_new), obs)
+        lo, hi = spec.healthy_range
+        health = obs[:, spec.health_index]
+        alive = alive & (health >= lo) & (health <= hi)
+    if not terminates:
+        lengths += steps
+        count = float(N * steps)
+    else:
+        count = float(lengths.sum().item())
+    result = (fitness, (count, obs_sum, obs_sumsq))
+    return result + (lengths,) if return_steps else result

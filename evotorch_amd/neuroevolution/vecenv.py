@@ -85,6 +85,12 @@ class SyntheticTorchEnv:
         self._obs = o_new
         self._t += 1
         done = torch.full((self.num_envs,), self._t >= s.episode_length, dtype=torch.bool, device=self.device)
+        if s.terminates:
+            # the fused rollout's rule on this path's fp32 observation: done
+            # after the step that leaves the healthy range (a NaN leaves it)
+            lo, hi = s.healthy_range
+            health = o_new[:, s.health_index]
+            done = done | ~((health >= lo) & (health <= hi))
         return o_new, reward, done
 
 

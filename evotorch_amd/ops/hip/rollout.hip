@@ -2,10 +2,11 @@
 // through the synthetic vectorized environment, one kernel launch per
 // generation (SURVEY.md §3.4 — the VecGymNE hot loop, collapsed).
 //
-// This file holds the dispatcher `rollout_linear` — the one place that
-// validates, fills RolloutArgs, picks a kernel and sums the obs-stat
-// partials — and v6, the general kernel (any geometry, linear or MLP
-// policy). The Humanoid-geometry kernels live in rollout_v7.hip (linear,
+// This file holds the dispatcher `rollout_linear` — with `prepare_rollout`
+// the one place that validates, fills RolloutArgs, picks a kernel and sums
+// the obs-stat partials — its early-terminating sibling
+// `rollout_terminating`, and v6, the general kernel (any geometry, linear
+// or MLP policy). The Humanoid-geometry kernels live in rollout_v7.hip (linear,
 // MFMA) and rollout_m7.hip (MLP-64); shared helpers in rollout_common.h.
 //
 // Policies: linear (obs -> act) or one-hidden-layer tanh MLP
@@ -43,6 +44,9 @@
 //   o'    = tanh(Σ_i U_T[i]·h[i] + Σ_m D2_T[m]·a[m] + c)
 //   r     = wr·o' + alive_bonus − act_cost·‖a‖²/A
 //   o₀    = 0.1·philox_normal(member);  fitness = Σ_t r_t
+// Terminating variant: a member is done after the step whose
+// bf16(o'[health_index]) is outside [healthy_lo, healthy_hi]; Σ_t then
+// runs over its len steps, and len goes to steps_out.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -71,6 +75,7 @@ struct V6Layout {
     size_t V, U_pair, D2_pair, c, wr, mean, istd, scratch;  // shared environment
     size_t member0, member_stride;                          // member m's region starts at member0 + m * member_stride
     size_t W1, b1, W2, b2, hid, obs, obsn, h, act;          // within a member's region
+    size_t flags;                                           // int [members] alive flags (terminating kernel only)
     size_t bytes;
 };
 
@@ -106,8 +111,11 @@ __host__ __device__ inline V6Layout v6_layout(int O, int A, int R, int H, int me
     l.act = take((size_t)l.A_PAD * 2);              // bf16 [A_PAD]
     l.member_stride = at;
     // 64 B of tail slack the launcher has always requested; kept so the
-    // footprint and the two-member threshold stay where they were
-    l.bytes = l.member0 + (size_t)members * l.member_stride + 64;
+    // footprint and the two-member threshold stay where they were. The
+    // terminating kernel keeps its alive flags there (every region before
+    // it is a multiple of 4 B: O and H are even).
+    l.flags = l.member0 + (size_t)members * l.member_stride;
+    l.bytes = l.flags + 64;
     return l;
 }
 
@@ -123,7 +131,10 @@ struct OutDesc {
     bool valid;
 };
 
-template <int kGroup, int kMembers>
+// kTerm adds early episode termination (see the flag protocol at the step
+// loop); everything it needs sits behind `if constexpr (kTerm)`, and a live
+// member runs the same arithmetic sequence in both instantiations.
+template <int kGroup, int kMembers, bool kTerm>
 __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args) {
     const int O = args.obs_dim, A = args.act_dim, R = args.rank, H = args.hidden;
     const int tid = threadIdx.x;
@@ -192,6 +203,11 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
             mean_l[j] = env.mean[j];
             istd_l[j] = 1.0f / env.std[j];
         }
+    }
+    // alive flags: 1 for a live slot, 0 for the empty slot of a half-live block
+    [[maybe_unused]] int* alive_l = reinterpret_cast<int*>(lds_raw + lay.flags);
+    if constexpr (kTerm) {
+        if (tid < kMembers) alive_l[tid] = tid < live_members;
     }
     // ---- stage members: weights, pads, initial observations ----
 #pragma unroll
@@ -304,6 +320,20 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
         actsq_part[m] = 0.0f;
     }
     float stat_sum[2] = {0.0f, 0.0f}, stat_sumsq[2] = {0.0f, 0.0f};
+    // kTerm: this step's alive flags and the episode lengths, the same in
+    // every thread of the block
+    [[maybe_unused]] int alive_r[kMembers];
+    [[maybe_unused]] int len_r[kMembers];
+#pragma unroll
+    for (int m = 0; m < kMembers; ++m) {
+        alive_r[m] = 1;
+        len_r[m] = 0;
+    }
+    // does member m take part in this step? (always, without termination)
+    const auto member_on = [&alive_r](int m) -> bool {
+        if constexpr (kTerm) return (m == 0 ? alive_r[0] : alive_r[kMembers - 1]) != 0;
+        return true;
+    };
 
     // initial normalization (later steps fuse it into phase 2's epilogue)
     for (int j = tid; j < live_members * O; j += blockDim.x) {
@@ -314,6 +344,11 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
     }
     __syncthreads();
 
+    // an output is worked on when its table entry is in use and (kTerm) its
+    // member is still alive: a done member's dots, stores and action cost
+    // are skipped. The test is uniform over the 8-lane group.
+#define DESC_ON(d) ((d).valid && member_on((d).member))
+
     // group-dot worker: acc[r] = descs[r].row · descs[r].vec  (length
     // 2*n_pairs), reduced across the kGroup lanes of the group
 #define GROUP_DOTS(descs, NR, n_pairs_expr, acc)                                              \
@@ -321,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
         const int np = (n_pairs_expr);                                                        \
         _Pragma("unroll") for (int r = 0; r < (NR); ++r) acc[r] = 0.0f;                       \
         _Pragma("unroll") for (int r = 0; r < (NR); ++r) {                                    \
-            if (!descs[r].valid) continue;                                                    \
+            if (!DESC_ON(descs[r])) continue;                                                 \
             const __bf16* row = descs[r].row;                                                 \
             const __bf16* vec = descs[r].vec;                                                 \
             float a0 = 0.0f, a1 = 0.0f;                                                       \
@@ -353,14 +388,14 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
         }                                                                                     \
         _Pragma("unroll") for (int r = 0; r < (NR); ++r) {                                    \
             /* VALU DPP group reduce; group sums land in glane == kGroup-1 */                 \
-            if (descs[r].valid) acc[r] = group8_sum_dpp(acc[r]);                              \
+            if (DESC_ON(descs[r])) acc[r] = group8_sum_dpp(acc[r]);                           \
         }                                                                                     \
     }
 
 #define DOT_EPILOGUE(descs, NR, acc)                                                          \
     if (glane == kGroup - 1) {                                                                \
         _Pragma("unroll") for (int r = 0; r < (NR); ++r) {                                    \
-            if (!descs[r].valid) continue;                                                    \
+            if (!DESC_ON(descs[r])) continue;                                                 \
             if (descs[r].kind == 1) {                                                         \
                 const float a = fminf(fmaxf(acc[r] + *descs[r].bias, -1.0f), 1.0f);           \
                 *descs[r].dst = f2b(a);                                                       \
@@ -375,7 +410,23 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
         }                                                                                     \
     }
 
+    // Termination (kTerm). alive_l[m] in LDS is cleared in the dynamics phase
+    // by the one thread that owns (m, health_index); every thread copies the
+    // flags into registers at the top of the next step. Those reads come
+    // after the end-of-step barrier and before the phase-A barrier, the next
+    // write comes after it: no race and no extra barrier. All threads read
+    // the same flags, so the early exit is block-uniform.
     for (int t = 0; t < args.steps; ++t) {
+        if constexpr (kTerm) {
+            int any_alive = 0;
+#pragma unroll
+            for (int m = 0; m < kMembers; ++m) {
+                alive_r[m] = alive_l[m];
+                len_r[m] += alive_r[m];
+                any_alive |= alive_r[m];
+            }
+            if (!any_alive) break;
+        }
         // ---- phase A: hidden (or action) + dynamics-factor dots ----
         float accA[kRoundsA];
         GROUP_DOTS(descA, kRoundsA, O / 2, accA);
@@ -393,6 +444,7 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
         // ---- dynamics phase: per-thread dims, norm fused in epilogue ----
         for (int j = tid; j < live_members * O; j += blockDim.x) {
             const int m = j / O, jo = j % O;
+            if (!member_on(m)) continue;  // a done member's sums and observation stay as they are
             float uacc = c_l[jo], dacc = 0.0f;
             const __bf16* hv = sel2(m, h_b[0], h_b[kMembers - 1]);
             const __bf16* av = sel2(m, act_b[0], act_b[kMembers - 1]);
@@ -419,12 +471,19 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
             __bf16* obsn_m = sel2(m, obsn_b[0], obsn_b[kMembers - 1]);
             obs_m[jo] = ob;
             obsn_m[jo] = f2b((b2f(ob) - mean_l[jo]) * istd_l[jo]);
+            if constexpr (kTerm) {
+                // done after this step: the bf16 value the policy would see
+                // next is outside the healthy range (a NaN is outside)
+                const float health = b2f(ob);
+                if (jo == args.health_index && !(args.healthy_lo <= health && health <= args.healthy_hi)) alive_l[m] = 0;
+            }
         }
         __syncthreads();
     }
 
 #undef GROUP_DOTS
 #undef DOT_EPILOGUE
+#undef DESC_ON
 
     // ---- wrap-up: per-member fitness reductions + obs-stat slices ----
 #pragma unroll
@@ -434,9 +493,12 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
         __syncthreads();
         const float act_total = block_reduce_sum<false>(actsq_part[m], scratch);
         __syncthreads();
+        // the alive bonus is paid per step survived
+        const int steps_m = kTerm ? len_r[m] : args.steps;
         if (tid == 0) {
             args.fitness_out[base_member + m] =
-                total + args.alive_bonus * args.steps - args.act_cost * act_total / (float)A;
+                total + args.alive_bonus * steps_m - args.act_cost * act_total / (float)A;
+            if constexpr (kTerm) args.steps_out[base_member + m] = steps_m;
         }
     }
     // per-(block, member) stat slices: the j-loop visits each (m, jo) pair
@@ -456,15 +518,15 @@ __global__ __launch_bounds__(512, 2) void rollout_linear_kernel(RolloutArgs args
 
 constexpr int kV6Threads = 512;
 
-template <int kGroup, int kMembers>
+template <int kGroup, int kMembers, bool kTerm>
 static void launch_rollout_v6(const RolloutArgs& args, int n_blocks, size_t lds_bytes, hipStream_t stream) {
     static bool attr_set = false;
     if (!attr_set && lds_bytes > 64 * 1024) {
-        allow_max_dynamic_lds(reinterpret_cast<const void*>(&rollout_linear_kernel<kGroup, kMembers>));
+        allow_max_dynamic_lds(reinterpret_cast<const void*>(&rollout_linear_kernel<kGroup, kMembers, kTerm>));
         attr_set = true;
     }
-    hipLaunchKernelGGL((rollout_linear_kernel<kGroup, kMembers>), dim3(n_blocks), dim3(kV6Threads), lds_bytes, stream,
-                       args);
+    hipLaunchKernelGGL((rollout_linear_kernel<kGroup, kMembers, kTerm>), dim3(n_blocks), dim3(kV6Threads), lds_bytes,
+                       stream, args);
 }
 
 // v6 members per block: two where they fit in LDS, else one. Checks the
@@ -480,10 +542,20 @@ static int v6_members_per_block(int O, int A, int R, int H) {
     return members;
 }
 
-torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
-                             int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
-                             double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
-                             c10::optional<torch::Tensor> seed_buf) {
+// A validated rollout call: the checked operands turned into kernel
+// arguments (all but obs_stats_out, which each entry point sizes for the
+// kernel it picks) and the fitness tensor the kernel writes.
+struct RolloutCall {
+    RolloutArgs args;
+    int n, O, A, R, H;
+    torch::Tensor fitness;
+};
+
+static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Tensor& env_blob,
+                                   const torch::Tensor& obs_stats_out, int64_t obs_dim, int64_t act_dim, int64_t rank,
+                                   int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
+                                   int64_t member_offset, int64_t policy_hidden,
+                                   const c10::optional<torch::Tensor>& seed_buf) {
     const unsigned long long* seed_ptr = seed_buf.has_value() ? device_i64_scalar(*seed_buf, "seed_buf") : nullptr;
     check_primary(params, "params", 2);
     TORCH_CHECK(params.scalar_type() == at::ScalarType::Float, "params must be fp32");
@@ -497,12 +569,15 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
     // the sum of the EnvBlob layout in rollout_common.h
     check_operand(env_blob, "env_blob", params, (2 * (int64_t)R + A + 4) * O);
     check_operand(obs_stats_out, "obs_stats_out", params, 2 * (int64_t)O);
-    auto fitness = torch::empty({n}, params.options());
 
-    RolloutArgs args;
+    RolloutCall call;
+    call.n = n; call.O = O; call.A = A; call.R = R; call.H = H;
+    call.fitness = torch::empty({n}, params.options());
+    RolloutArgs& args = call.args;
     args.params = params.data_ptr<float>();
     args.env_blob = env_blob.data_ptr<float>();
-    args.fitness_out = fitness.data_ptr<float>();
+    args.fitness_out = call.fitness.data_ptr<float>();
+    args.obs_stats_out = nullptr;
     args.n_members = n;
     args.member_offset = (long)member_offset;
     args.obs_dim = O; args.act_dim = A; args.rank = R; args.hidden = H;
@@ -511,6 +586,20 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
     args.act_cost = (float)act_cost;
     args.init_seed = (unsigned long long)init_seed;
     args.seed_ptr = seed_ptr;
+    args.health_index = 0;
+    args.healthy_lo = args.healthy_hi = 0.0f;
+    args.steps_out = nullptr;
+    return call;
+}
+
+torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
+                             int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
+                             double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
+                             c10::optional<torch::Tensor> seed_buf) {
+    RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
+                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf);
+    RolloutArgs& args = call.args;
+    const int n = call.n, O = call.O, A = call.A, R = call.R, H = call.H;
 
     // v7 (MFMA, linear) and m7 (MLP-64) serve the Humanoid geometry; v6
     // covers every other geometry and policy width, and that geometry too
@@ -532,12 +621,50 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
     } else if (use_m7) {
         launch_rollout_m7(args, n, stream);
     } else if (members == 2) {
-        launch_rollout_v6<8, 2>(args, n_blocks, v6_layout(O, A, R, H, 2).bytes, stream);
+        launch_rollout_v6<8, 2, false>(args, n_blocks, v6_layout(O, A, R, H, 2).bytes, stream);
     } else {
-        launch_rollout_v6<8, 1>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
+        launch_rollout_v6<8, 1, false>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
     }
     obs_stats_out.add_(stat_partials.sum(0));
-    return fitness;
+    return call.fitness;
+}
+
+// rollout_linear with early episode termination: member m is done after the
+// step whose bf16(o'[health_index]) leaves [healthy_lo, healthy_hi], and its
+// length goes to steps_out[m]. Always the terminating v6 kernel, at every
+// geometry (v7 and m7 do not terminate).
+torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
+                                  torch::Tensor steps_out, int64_t obs_dim, int64_t act_dim, int64_t rank,
+                                  int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
+                                  int64_t member_offset, int64_t policy_hidden, int64_t health_index,
+                                  double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf) {
+    RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
+                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf);
+    RolloutArgs& args = call.args;
+    const int n = call.n, O = call.O, A = call.A, R = call.R, H = call.H;
+    check_operand_as(steps_out, "steps_out", params, at::ScalarType::Int, n);
+    TORCH_CHECK(health_index >= 0 && health_index < O, "health_index must be in [0, ", O, "), got ", health_index);
+    // written so that a NaN bound fails it too
+    TORCH_CHECK(healthy_lo <= healthy_hi, "healthy range must satisfy lo <= hi, got (", healthy_lo, ", ", healthy_hi,
+                ")");
+    args.health_index = (int)health_index;
+    args.healthy_lo = (float)healthy_lo;
+    args.healthy_hi = (float)healthy_hi;
+    args.steps_out = steps_out.data_ptr<int>();
+
+    const int members = v6_members_per_block(O, A, R, H);
+    const int n_blocks = (n + members - 1) / members;
+    auto stat_partials = torch::zeros({(int64_t)n_blocks * members, 2 * (int64_t)O}, params.options());
+    args.obs_stats_out = stat_partials.data_ptr<float>();
+
+    auto stream = at::cuda::getCurrentCUDAStream();
+    if (members == 2) {
+        launch_rollout_v6<8, 2, true>(args, n_blocks, v6_layout(O, A, R, H, 2).bytes, stream);
+    } else {
+        launch_rollout_v6<8, 1, true>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
+    }
+    obs_stats_out.add_(stat_partials.sum(0));
+    return call.fitness;
 }
 
 }  // namespace ea

@@ -80,6 +80,12 @@ struct RolloutArgs {
     unsigned long long init_seed;
     const unsigned long long* seed_ptr;  // device episode seed (hipGraph-safe); overrides init_seed
     int hidden;               // policy hidden width, 0 = linear policy
+    // early termination (terminating v6 only; the other kernels ignore these):
+    // a member is done after the step whose bf16(o'[health_index]) leaves
+    // [healthy_lo, healthy_hi] (NaN counts as outside)
+    int health_index;
+    float healthy_lo, healthy_hi;
+    int* steps_out;           // [n_members] episode lengths
 };
 
 // env_blob layout (fp32, SyntheticEnvSpec.env_blob): V [R][O] · U_T [R][O] ·
