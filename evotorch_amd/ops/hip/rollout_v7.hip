@@ -22,19 +22,25 @@
 //
 // Policy phase (act = clamp(W·obsn + b), no shared operand — not
 // MFMA-shaped): per-member weights stay in REGISTERS, one 32-lane
-// half-wave per member, 12 obs columns per lane, 17 accumulators of
-// v_dot2. Actions 0..15 are then reduced with a TRANSPOSING butterfly on
-// the VALU pipe: each level a lane keeps half of its accumulators and
-// hands the other half to a partner (16→8→4→2→1 over lane^1, lane^2,
-// lane^4, lane^8 with DPP quad_perm / row_shl+row_shr / row_ror, then one
-// v_permlane16_swap add across the two rows), so 16 lanes end up with one
-// finished action each — ~50 ops instead of 16 × 5 full-width DPP adds,
-// in the same summation tree. Action 16 keeps a plain 5-step DPP reduce
-// into lane 31. The tail (bias, clamp, bf16 convert, hact store) then runs
-// ONCE on those 17 lanes, lane-parallel. The tail lanes also publish the
-// fp32 actions, and after the barrier the half-wave folds them into Σa² as
-// one fma chain in action order, sliced under the GEMM2 epilogue. No ds_bpermute shuffles in the
-// loop (see reduce32_dpp).
+// half-wave per member, 12 obs columns per lane (three 8-byte LDS reads),
+// 17 accumulators of v_dot2; the first column pair uses the three-operand
+// v_dot2 with a constant 0, so no accumulator is zeroed first. Actions
+// 0..15 are then reduced with a TRANSPOSING butterfly on the VALU pipe:
+// each level a lane keeps half of its accumulators and adds the partner's
+// other half (16→8→4→2→1 over lane^1, lane^2, lane^4, lane^8 with DPP
+// quad_perm / row_shl+row_shr / row_ror, then one v_permlane16_swap add
+// across the two rows), so 16 lanes end up with one finished action each —
+// 15 DPP adds instead of 16 × 5 full-width ones, in the same summation
+// tree. The weight rows are loaded permuted (register a of a lane holds
+// action a ^ perm(lane), perm = the lane's low four bits reversed), which
+// makes "the half to keep" the low registers on every lane: no level
+// selects. Action 16 keeps a plain 5-step DPP reduce into lane 31. The
+// tail (bias, clamp, bf16 convert, hact store) then runs ONCE on those 17
+// lanes, lane-parallel. The tail lanes also publish the fp32 actions, and
+// after the barrier the half-wave reads its member's row back in 16-byte
+// words and folds it into Σa² as one fma chain in action order, sliced
+// under the GEMM2 epilogue. No ds_bpermute shuffles in the loop (see
+// reduce32_dpp).
 //
 // GEMM1 is wave 0's alone: 24 LDS fragment reads and 12 MFMAs per step,
 // ahead of the wave's policy share. It is NOT hidden under the policy
@@ -85,26 +91,13 @@
 
 namespace ea {
 
-// One level of the transposing (halving) reduction inside a 16-lane DPP
-// row. A lane holds two partial sums, lo and hi; it keeps one of them
-// (hi when `up`, else lo), hands the other to its partner lane and adds
-// the partner's partial of the sum it kept. kCtrl must pair every lane
-// with a lane whose `up` is the opposite.
-template <int kCtrl>
-__device__ __forceinline__ float dpp_halve(float lo, float hi, bool up) {
-    const float keep = up ? hi : lo;
-    const float send = up ? lo : hi;
-    return dpp_add_from<kCtrl>(keep, send);
-}
-
-// The level for partner lane^4, which no single DPP control reaches:
-// banks 0/2 of a row (lanes 0-3, 8-11) read lane+4, banks 1/3 lane-4.
-__device__ __forceinline__ float dpp_halve_xor4(float lo, float hi, bool up) {
-    const float keep = up ? hi : lo;
-    const int send = __builtin_bit_cast(int, up ? lo : hi);
+// x + (y of lane^4), a partner no single DPP control reaches: banks 0/2
+// of a row (lanes 0-3, 8-11) read lane+4, banks 1/3 lane-4.
+__device__ __forceinline__ float dpp_add_from_xor4(float x, float y) {
+    const int send = __builtin_bit_cast(int, y);
     int moved = __builtin_amdgcn_update_dpp(0, send, 0x104, 0xf, 0x5, false);  // row_shl:4
     moved = __builtin_amdgcn_update_dpp(moved, send, 0x114, 0xf, 0xa, false);  // row_shr:4
-    return keep + __builtin_bit_cast(float, moved);
+    return x + __builtin_bit_cast(float, moved);
 }
 
 // Sum of the two 16-lane rows of a half-wave, in both rows:
@@ -120,6 +113,7 @@ __device__ __forceinline__ float row_pair_add(float x) {
 }
 
 typedef __attribute__((ext_vector_type(2))) float floatx2;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 // Two floats to bf16 with ONE v_cvt_pk_bf16_f32 (a scalar f2b spends the
 // same instruction on one value); x is the low half.
@@ -133,6 +127,70 @@ __device__ __forceinline__ floatx2 b2f_pair(bf16x2 v) {
     const unsigned u = __builtin_bit_cast(unsigned, v);
     const floatx2 f = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
     return f;
+}
+
+// The first column pair of the policy dot products, acc[a] = w[a][0]·o + 0,
+// in the three-operand form v_dot2_f32_bf16 with the inline constant 0: the
+// two-operand v_dot2c the builtin selects needs its accumulator zeroed by a
+// v_mov first. Several at once (9 + 8: an asm statement takes 30 operands)
+// so that one trailing s_nop 2 covers the three wait states a dot result
+// needs before another VALU opcode (the v_dot2c of the next pair) may read
+// it: the compiler's hazard recognizer cannot see into the string. The
+// outputs are early-clobber, a later line still reads its inputs. Whether
+// this form rounds like v_dot2c on a zeroed accumulator is not documented;
+// on the MI355X it does, in every recorded-bits test
+// (tests/golden/rollout_v7_bits*.npz) and in bench.py --dump-outputs.
+template <int kCols>
+__device__ __forceinline__ void dot2_first_pair9(float* acc, const bf16x2 (*w)[kCols], bf16x2 o2) {
+    const unsigned w0 = __builtin_bit_cast(unsigned, w[0][0]);
+    const unsigned w1 = __builtin_bit_cast(unsigned, w[1][0]);
+    const unsigned w2 = __builtin_bit_cast(unsigned, w[2][0]);
+    const unsigned w3 = __builtin_bit_cast(unsigned, w[3][0]);
+    const unsigned w4 = __builtin_bit_cast(unsigned, w[4][0]);
+    const unsigned w5 = __builtin_bit_cast(unsigned, w[5][0]);
+    const unsigned w6 = __builtin_bit_cast(unsigned, w[6][0]);
+    const unsigned w7 = __builtin_bit_cast(unsigned, w[7][0]);
+    const unsigned w8 = __builtin_bit_cast(unsigned, w[8][0]);
+    asm(
+        "v_dot2_f32_bf16 %0, %9, %18, 0\n\t"
+        "v_dot2_f32_bf16 %1, %10, %18, 0\n\t"
+        "v_dot2_f32_bf16 %2, %11, %18, 0\n\t"
+        "v_dot2_f32_bf16 %3, %12, %18, 0\n\t"
+        "v_dot2_f32_bf16 %4, %13, %18, 0\n\t"
+        "v_dot2_f32_bf16 %5, %14, %18, 0\n\t"
+        "v_dot2_f32_bf16 %6, %15, %18, 0\n\t"
+        "v_dot2_f32_bf16 %7, %16, %18, 0\n\t"
+        "v_dot2_f32_bf16 %8, %17, %18, 0\n\t"
+        "s_nop 2"
+        : "=&v"(acc[0]), "=&v"(acc[1]), "=&v"(acc[2]), "=&v"(acc[3]), "=&v"(acc[4]), "=&v"(acc[5]), "=&v"(acc[6]),
+          "=&v"(acc[7]), "=&v"(acc[8])
+        : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "v"(w5), "v"(w6), "v"(w7), "v"(w8),
+          "v"(__builtin_bit_cast(unsigned, o2)));
+}
+template <int kCols>
+__device__ __forceinline__ void dot2_first_pair8(float* acc, const bf16x2 (*w)[kCols], bf16x2 o2) {
+    const unsigned w0 = __builtin_bit_cast(unsigned, w[0][0]);
+    const unsigned w1 = __builtin_bit_cast(unsigned, w[1][0]);
+    const unsigned w2 = __builtin_bit_cast(unsigned, w[2][0]);
+    const unsigned w3 = __builtin_bit_cast(unsigned, w[3][0]);
+    const unsigned w4 = __builtin_bit_cast(unsigned, w[4][0]);
+    const unsigned w5 = __builtin_bit_cast(unsigned, w[5][0]);
+    const unsigned w6 = __builtin_bit_cast(unsigned, w[6][0]);
+    const unsigned w7 = __builtin_bit_cast(unsigned, w[7][0]);
+    asm(
+        "v_dot2_f32_bf16 %0, %8, %16, 0\n\t"
+        "v_dot2_f32_bf16 %1, %9, %16, 0\n\t"
+        "v_dot2_f32_bf16 %2, %10, %16, 0\n\t"
+        "v_dot2_f32_bf16 %3, %11, %16, 0\n\t"
+        "v_dot2_f32_bf16 %4, %12, %16, 0\n\t"
+        "v_dot2_f32_bf16 %5, %13, %16, 0\n\t"
+        "v_dot2_f32_bf16 %6, %14, %16, 0\n\t"
+        "v_dot2_f32_bf16 %7, %15, %16, 0\n\t"
+        "s_nop 2"
+        : "=&v"(acc[0]), "=&v"(acc[1]), "=&v"(acc[2]), "=&v"(acc[3]), "=&v"(acc[4]), "=&v"(acc[5]), "=&v"(acc[6]),
+          "=&v"(acc[7])
+        : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "v"(w5), "v"(w6), "v"(w7),
+          "v"(__builtin_bit_cast(unsigned, o2)));
 }
 
 // Compile-time geometry and the dynamic-LDS layout (byte offsets), stated
@@ -161,7 +219,9 @@ struct V7Layout {
     static constexpr int ud = d2last + OP * 4;              // bf16 [OP][KU] k-major GEMM2 B
     static constexpr int bytes = ud + OP * KU * 2;
     static_assert(bytes <= 160 * 1024, "v7 LDS footprint exceeds the 160 KB of a gfx950 workgroup");
-    static_assert(actf % 4 == 0 && ud % 16 == 0 && v % 16 == 0, "misaligned LDS region");
+    static_assert(actf % 16 == 0 && ud % 16 == 0 && v % 16 == 0, "misaligned LDS region");
+    // the policy phase reads a lane's obsn chunk as 8-byte words
+    static_assert(obsn % 8 == 0 && (OPS * 2) % 8 == 0 && (OP / 32) % 4 == 0, "misaligned policy obs chunk");
 };
 
 // All guards constant-fold: a runtime-guarded W-load was measured to
@@ -242,20 +302,26 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     // ---- per-member policy weights in registers -----------------------------
     // half-wave (32 lanes) per member: member = 2*wave + (lane>>5);
     // lane owns obsn columns [l32*kChunk, l32*kChunk + kChunk).
+    // Register a < 16 holds weight row a ^ perm, perm being the lane's low
+    // four bits reversed: the transposing reduction of the policy phase then
+    // needs no per-lane choice of what to keep (see there). Row 16 stays put.
+    static_assert(A_MAX == 17, "the policy reduction is laid out for 16 butterfly actions and one plain one");
     const int l32 = lane & 31;
     const int my_member = 2 * wave + (lane >> 5);
+    const int perm = ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
     bf16x2 w_frag[A_MAX][kChunk / 2];
     {
         const float* W = args.params + (long)(base_member + min(my_member, live - 1)) * ((long)A * O + A);
         const int cbase = l32 * kChunk;
 #pragma unroll
         for (int a = 0; a < A_MAX; ++a) {
+            const float* Wa = W + (long)(a < 16 ? (a ^ perm) : a) * O;
 #pragma unroll
             for (int p = 0; p < kChunk / 2; ++p) {
                 const int k0 = cbase + 2 * p;
                 bf16x2 w2;
-                w2.x = (a < A && k0 < O) ? f2b(W[(long)a * O + k0]) : f2b(0.0f);
-                w2.y = (a < A && k0 + 1 < O) ? f2b(W[(long)a * O + k0 + 1]) : f2b(0.0f);
+                w2.x = (k0 < O) ? f2b(Wa[k0]) : f2b(0.0f);
+                w2.y = (k0 + 1 < O) ? f2b(Wa[k0 + 1]) : f2b(0.0f);
                 w_frag[a][p] = w2;
             }
         }
@@ -264,8 +330,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     // After the transposing reduction (see the policy phase) the first 16
     // lanes of the half-wave hold one finished action each; its lane 31
     // holds action A-1 from the plain reduction. Those 17 lanes run the tail.
-    const bool up0 = lane & 1, up1 = lane & 2, up2 = lane & 4, up3 = lane & 8;
-    const int my_act = (l32 == 31) ? 16 : ((up0 ? 8 : 0) + (up1 ? 4 : 0) + (up2 ? 2 : 0) + (up3 ? 1 : 0));
+    const int my_act = (l32 == 31) ? 16 : perm;
     const bool tail_lane = my_member < live && my_act < A && (l32 < 16 || l32 == 31);
     const float my_bias =
         tail_lane ? args.params[(long)(base_member + my_member) * (AO + A) + AO + my_act] : 0.0f;
@@ -297,6 +362,22 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
         obsn_l[j] = (jo < OP) ? f2b((b2f(obs_l[j]) - mean_l[jo]) * istd_l[jo]) : f2b(0.0f);
     }
     __syncthreads();
+
+    // Per-column constants of the lane's GEMM2 epilogue columns. They do not
+    // change during the episode, and a load inside the step loop cannot be
+    // hoisted over its barriers by the compiler, so read them once, here
+    // (staged before the barriers above).
+    float d2last_r[kTilesPerWave], c_r[kTilesPerWave], wr_r[kTilesPerWave], mean_r[kTilesPerWave],
+        istd_r[kTilesPerWave];
+#pragma unroll
+    for (int tw = 0; tw < kTilesPerWave; ++tw) {
+        const int col = (wave * kTilesPerWave + tw) * 16 + c_col;
+        d2last_r[tw] = d2last_l[col];
+        c_r[tw] = c_l[col];
+        wr_r[tw] = wr_l[col];
+        mean_r[tw] = mean_l[col];
+        istd_r[tw] = istd_l[col];
+    }
 
     // ---- episode state in registers ----
     float fit_part[4] = {0.f, 0.f, 0.f, 0.f};  // member rows (lane>>4)*4+reg of GEMM2
@@ -340,12 +421,20 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
         {
             float acc[A_MAX];
 #pragma unroll
-            for (int a = 0; a < A_MAX; ++a) acc[a] = 0.0f;
+            for (int a = 0; a < A_MAX; ++a) acc[a] = 0.0f;  // for the masked body's dead members only
             if (kFull || my_member < live) {
-                const __bf16* on = obsn_l + my_member * OPS + l32 * kChunk;
+                // the lane's chunk as 8-byte reads (ds_read_b64), two column pairs each
+                const bf16x4* on = reinterpret_cast<const bf16x4*>(obsn_l + my_member * OPS + l32 * kChunk);
 #pragma unroll
                 for (int p = 0; p < kChunk / 2; ++p) {
-                    const bf16x2 o2 = *reinterpret_cast<const bf16x2*>(on + 2 * p);
+                    const bf16x4 o4 = on[p / 2];
+                    const bf16x2 o2 = (p & 1) ? __builtin_shufflevector(o4, o4, 2, 3)
+                                              : __builtin_shufflevector(o4, o4, 0, 1);
+                    if (p == 0) {
+                        dot2_first_pair9(acc, w_frag, o2);
+                        dot2_first_pair8(acc + 9, w_frag + 9, o2);
+                        continue;
+                    }
 #pragma unroll
                     for (int a = 0; a < A_MAX; ++a) {
                         acc[a] = __builtin_amdgcn_fdot2_f32_bf16(w_frag[a][p], o2, acc[a], false);
@@ -355,23 +444,29 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
             // Transposing reduction of actions 0..15 over the half-wave's
             // 32 lanes: every level halves the accumulators a lane still
             // carries (16→8→4→2→1) while it doubles the lanes summed into
-            // them, ~50 VALU ops instead of 16 × 5 full-width adds. The
+            // them, 15 DPP adds instead of 16 × 5 full-width ones. The
             // levels pair lane^1, lane^2, lane^4, lane^8 and finally the
             // two rows — the same balanced tree, pair for pair, as the
             // row_shr 1/2/4/8 + row_bcast reduction action 16 still uses,
             // so every action sum has one summation order (and the bits
-            // the full-width reduction gave). A lane of either row ends
-            // up with action 8·bit0 + 4·bit1 + 2·bit2 + bit3 = my_act.
+            // the full-width reduction gave).
+            // No level selects what to keep: register i holds action
+            // i ^ perm, and the lane^1 partner (perm' = perm ^ 8) holds
+            // that same action in its register i + 8, since
+            // (i + 8) ^ perm' = i ^ perm for i < 8; likewise lane^2 with
+            // i + 4, lane^4 with i + 2 and lane^8 with i + 1. So a lane
+            // always keeps its low half and adds the partner's high half,
+            // and ends with action 0 ^ perm = my_act in register 0.
             // Identical in both half-waves and every wave, so a member's
             // arithmetic does not depend on its slot.
             float v8[8], v4[4], v2[2];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) v8[i] = dpp_halve<0xB1>(acc[i], acc[i + 8], up0);  // quad_perm:[1,0,3,2]
+            for (int i = 0; i < 8; ++i) v8[i] = dpp_add_from<0xB1>(acc[i], acc[i + 8]);  // quad_perm:[1,0,3,2]
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v4[i] = dpp_halve<0x4E>(v8[i], v8[i + 4], up1);    // quad_perm:[2,3,0,1]
+            for (int i = 0; i < 4; ++i) v4[i] = dpp_add_from<0x4E>(v8[i], v8[i + 4]);    // quad_perm:[2,3,0,1]
 #pragma unroll
-            for (int i = 0; i < 2; ++i) v2[i] = dpp_halve_xor4(v4[i], v4[i + 2], up2);
-            const float a_sum = row_pair_add(dpp_halve<0x128>(v2[0], v2[1], up3));         // row_ror:8
+            for (int i = 0; i < 2; ++i) v2[i] = dpp_add_from_xor4(v4[i], v4[i + 2]);
+            const float a_sum = row_pair_add(dpp_add_from<0x128>(v2[0], v2[1]));         // row_ror:8
             const float a_last = reduce32_dpp(acc[A_MAX - 1]);
             if (tail_lane) {
                 const float av = fminf(fmaxf(((l32 == 31) ? a_last : a_sum) + my_bias, -1.0f), 1.0f);
@@ -404,27 +499,30 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
             // fp32 actions the tail lanes just published. Every lane of the
             // half-wave runs its member's chain, branch-free and a slice
             // per tile, so its LDS and fma latencies hide under the
-            // epilogue; only lane 31's copy is used at wrap-up.
+            // epilogue; only lane 31's copy is used at wrap-up. The row is
+            // read as 16-byte words (ds_read_b128), each in the tile that
+            // first needs it.
             constexpr int kSqPerTile = (A_MAX + kTilesPerWave - 1) / kTilesPerWave;
-            const float* af = actf_l + my_member * AF;
+            const floatx4* af = reinterpret_cast<const floatx4*>(actf_l + my_member * AF);
+            floatx4 av[AF / 4];
             float sq = 0.0f;
 #pragma unroll
             for (int tw = 0; tw < kTilesPerWave; ++tw) {
-                float av_t[kSqPerTile];
 #pragma unroll
-                for (int u = 0; u < kSqPerTile; ++u) {
-                    const int a = tw * kSqPerTile + u;
-                    av_t[u] = (a < A_MAX) ? af[a] : 0.0f;
+                for (int w = 0; w < AF / 4; ++w) {
+                    // the tile whose slice [a_lo, a_hi) holds the word's first action
+                    const int a_lo = tw * kSqPerTile, a_hi = min(a_lo + kSqPerTile, A_MAX);
+                    if (4 * w >= a_lo && 4 * w < a_hi) av[w] = af[w];
                 }
                 const int col = (wave * kTilesPerWave + tw) * 16 + c_col;
                 floatx4 acc = {0.f, 0.f, 0.f, 0.f};
                 const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(ud_l + col * KU + g2_k0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
-                const float d2l = d2last_l[col];
-                const float cv = c_l[col];
-                const float wrv = wr_l[col];
-                const float mv = mean_l[col];
-                const float iv = istd_l[col];
+                const float d2l = d2last_r[tw];
+                const float cv = c_r[tw];
+                const float wrv = wr_r[tw];
+                const float mv = mean_r[tw];
+                const float iv = istd_r[tw];
                 float ssum = 0.0f, ssq = 0.0f;
                 float o_row[4];
 #pragma unroll
@@ -470,7 +568,8 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 stat_sumsq[tw] += ssq;
 #pragma unroll
                 for (int u = 0; u < kSqPerTile; ++u) {
-                    if (tw * kSqPerTile + u < A_MAX) sq = fmaf(av_t[u], av_t[u], sq);
+                    const int a = tw * kSqPerTile + u;
+                    if (a < A_MAX) sq = fmaf(av[a / 4][a % 4], av[a / 4][a % 4], sq);
                 }
             }
             actsq_total += sq;
