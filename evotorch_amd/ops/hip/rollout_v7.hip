@@ -28,7 +28,7 @@
 // 0..15 are then reduced with a TRANSPOSING butterfly on the VALU pipe:
 // each level a lane keeps half of its accumulators and adds the partner's
 // other half (16→8→4→2→1 over lane^1, lane^2, lane^4, lane^8 with DPP
-// quad_perm / row_shl+row_shr / row_ror, then one v_permlane16_swap add
+// quad_perm / bank-masked row_shl+row_shr / row_ror, then one v_permlane16_swap add
 // across the two rows), so 16 lanes end up with one finished action each —
 // 15 DPP adds instead of 16 × 5 full-width ones, in the same summation
 // tree. The weight rows are loaded permuted (register a of a lane holds
@@ -53,9 +53,15 @@
 // (T = 1000), so GEMM1 stays a block of its own.
 //
 // GEMM2 phase: hact is the MFMA A operand, [U;D2] the B operand; a lane's
-// D fragment is one obs column of four members. The epilogue quantizes
-// and normalizes the four rows in pairs (one packed bf16 conversion per
-// pair, 16-bit LDS stores of its halves).
+// D fragment is one obs column of four members. The epilogue treats the
+// four rows as the two pairs (0, 1) and (2, 3), in the registers the MFMA
+// left them in: the rank-1 term, + c, tanh_fast's multiply, e ± 1 and
+// final product, and the fitness fma run two-wide (v_pk_fma_f32,
+// v_pk_add_f32, v_pk_mul_f32: each half rounds like the scalar
+// instruction), only the clamp, v_exp_f32 and v_rcp_f32 per value; the
+// pair is quantized and normalized with one packed bf16 conversion each
+// (16-bit LDS stores of its halves). A column's (sum, sumsq) is one pair
+// too.
 //
 // The episode loop exists twice: a block whose 16 slots are all live
 // (every block when the population is a multiple of 16) runs a body
@@ -91,13 +97,25 @@
 
 namespace ea {
 
-// x + (y of lane^4), a partner no single DPP control reaches: banks 0/2
-// of a row (lanes 0-3, 8-11) read lane+4, banks 1/3 lane-4.
-__device__ __forceinline__ float dpp_add_from_xor4(float x, float y) {
-    const int send = __builtin_bit_cast(int, y);
-    int moved = __builtin_amdgcn_update_dpp(0, send, 0x104, 0xf, 0x5, false);  // row_shl:4
-    moved = __builtin_amdgcn_update_dpp(moved, send, 0x114, 0xf, 0xa, false);  // row_shr:4
-    return x + __builtin_bit_cast(float, moved);
+// out[i] = x[i] + (y[i] of lane^4), i = 0, 1: a partner no single DPP control
+// reaches. Banks 0/2 of a row (lanes 0-3, 8-11) read lane+4, banks 1/3
+// lane-4, as two bank-masked v_add_f32_dpp into one destination (a lane
+// outside the bank mask keeps what it has, so the pair writes every lane
+// once). Built from update_dpp this was two zero moves, two masked DPP moves
+// and the add per value. The compiler's hazard recognizer cannot see into the
+// string: the leading s_nop 1 gives the two wait states a DPP read needs
+// after the VALU write of x and y, the trailing one the same for the DPP and
+// v_permlane16_swap reads that follow. The outputs are early-clobber, the
+// second line of a pair still reads its inputs.
+__device__ __forceinline__ void dpp_add_from_xor4_x2(float* out, const float* x, const float* y) {
+    asm("s_nop 1\n\t"
+        "v_add_f32_dpp %0, %4, %2 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+        "v_add_f32_dpp %1, %5, %3 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+        "v_add_f32_dpp %0, %4, %2 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %1, %5, %3 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+        "s_nop 1"
+        : "=&v"(out[0]), "=&v"(out[1])
+        : "v"(x[0]), "v"(x[1]), "v"(y[0]), "v"(y[1]));
 }
 
 // Sum of the two 16-lane rows of a half-wave, in both rows:
@@ -117,16 +135,28 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 // Two floats to bf16 with ONE v_cvt_pk_bf16_f32 (a scalar f2b spends the
 // same instruction on one value); x is the low half.
-__device__ __forceinline__ bf16x2 f2b_pair(float lo, float hi) {
-    const floatx2 v = {lo, hi};
-    return __builtin_convertvector(v, bf16x2);
-}
+__device__ __forceinline__ bf16x2 f2b_pair(floatx2 v) { return __builtin_convertvector(v, bf16x2); }
 
 // ... and back: the low half shifts up, the high half is masked in place.
 __device__ __forceinline__ floatx2 b2f_pair(bf16x2 v) {
     const unsigned u = __builtin_bit_cast(unsigned, v);
     const floatx2 f = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
     return f;
+}
+
+// tanh_fast (rollout_common.h) on two values, the same operations with the
+// same roundings: the multiply, e + 1, e - 1 and the final product two-wide,
+// the clamp (v_med3_f32), v_exp_f32 and v_rcp_f32 per element, for which no
+// two-wide instruction exists. Contraction is off: a caller's add must not
+// merge with the final product into an fma.
+__device__ __forceinline__ floatx2 tanh_fast_pair(floatx2 x) {
+#pragma clang fp contract(off)
+    const floatx2 xc = {fminf(fmaxf(x.x, -15.0f), 15.0f), fminf(fmaxf(x.y, -15.0f), 15.0f)};
+    const floatx2 t = xc * __builtin_bit_cast(float, 0x4038aa3bu);
+    const floatx2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+    const floatx2 d = e + 1.0f;
+    const floatx2 rcp = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+    return (e - 1.0f) * rcp;
 }
 
 // The first column pair of the policy dot products, acc[a] = w[a][0]·o + 0,
@@ -380,10 +410,9 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     }
 
     // ---- episode state in registers ----
-    float fit_part[4] = {0.f, 0.f, 0.f, 0.f};  // member rows (lane>>4)*4+reg of GEMM2
+    floatx2 fit_part[2] = {};                  // member rows (lane>>4)*4 + {0,1}, {2,3} of GEMM2
     float actsq_total = 0.0f;                  // my_member's Σa² (lane 31 of the half-wave publishes it)
-    float stat_sum[kTilesPerWave] = {};        // per owned obs column
-    float stat_sumsq[kTilesPerWave] = {};
+    floatx2 stat[kTilesPerWave] = {};          // (sum, sumsq) per owned obs column
 
     // the 16 rows of an MFMA A/D fragment are exactly the block's member slots
     static_assert(kM == 16, "GEMM1/GEMM2 fragments address member rows 0..15 unguarded");
@@ -464,8 +493,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
             for (int i = 0; i < 8; ++i) v8[i] = dpp_add_from<0xB1>(acc[i], acc[i + 8]);  // quad_perm:[1,0,3,2]
 #pragma unroll
             for (int i = 0; i < 4; ++i) v4[i] = dpp_add_from<0x4E>(v8[i], v8[i + 4]);    // quad_perm:[2,3,0,1]
-#pragma unroll
-            for (int i = 0; i < 2; ++i) v2[i] = dpp_add_from_xor4(v4[i], v4[i + 2]);
+            dpp_add_from_xor4_x2(v2, v4, v4 + 2);
             const float a_sum = row_pair_add(dpp_add_from<0x128>(v2[0], v2[1]));         // row_ror:8
             const float a_last = reduce32_dpp(acc[A_MAX - 1]);
             if (tail_lane) {
@@ -474,6 +502,11 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 *my_actf = av;
             }
         }
+        // h goes to hact only here, after wave 0's policy share. Storing it
+        // at the end of the GEMM1 region takes four v_mov 0 off every wave
+        // but measured 17 µs per launch slower (T = 1000): wave 0 is the
+        // barrier straggler, and the conversions and stores then sit ahead
+        // of its dot products.
         if (wave == 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -488,11 +521,12 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
         {
             const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(hact_l + g2_row * KS + g2_k0);
             // per-member act[A-1] for the rank-1 term, indexed by C rows
-            float a16[4];
+            floatx2 a16[2];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = c_row0 + r;
-                a16[r] = b2f(hact_l[m * KS + 32]);
+            for (int q = 0; q < 2; ++q) {
+                const int m = c_row0 + 2 * q;
+                a16[q].x = b2f(hact_l[m * KS + 32]);
+                a16[q].y = b2f(hact_l[(m + 1) * KS + 32]);
             }
             // Σa² of the step, as ONE fma chain in action order per member
             // (the summation order the fitness has always had), from the
@@ -518,54 +552,66 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 floatx4 acc = {0.f, 0.f, 0.f, 0.f};
                 const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(ud_l + col * KU + g2_k0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
-                const float d2l = d2last_r[tw];
-                const float cv = c_r[tw];
-                const float wrv = wr_r[tw];
-                const float mv = mean_r[tw];
-                const float iv = istd_r[tw];
+                const floatx2 d2l = {d2last_r[tw], d2last_r[tw]};
+                const floatx2 cv = {c_r[tw], c_r[tw]};
+                const floatx2 wrv = {wr_r[tw], wr_r[tw]};
+                const floatx2 mv = {mean_r[tw], mean_r[tw]};
+                const floatx2 iv = {istd_r[tw], istd_r[tw]};
+                // The four rows as the two pairs (0, 1) and (2, 3), which the
+                // MFMA result already holds in consecutive registers: every
+                // step of the epilogue that has a two-wide fp32 instruction
+                // (v_pk_fma_f32, v_pk_add_f32, v_pk_mul_f32; each half rounds
+                // like the scalar instruction) runs once per pair.
+                floatx2 o_pair[2];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const floatx2 accq = {acc[2 * q], acc[2 * q + 1]};
+                    o_pair[q] = tanh_fast_pair(__builtin_elementwise_fma(a16[q], d2l, accq) + cv);
+                    fit_part[q] = __builtin_elementwise_fma(wrv, o_pair[q], fit_part[q]);
+                }
+                // Statistics over the live rows, one chain in row order per
+                // column. Pad columns (col >= O) need no mask: their c, d2last
+                // and [U;D2] row are 0, so o = tanh_fast(0) = +0 exactly, and
+                // their sums are never stored. Row 0 starts the sums: 0 + o
+                // and fma(o, o, 0) give the same bits (tanh_fast never
+                // returns -0) but cost an op each.
+                const float o_row[4] = {o_pair[0].x, o_pair[0].y, o_pair[1].x, o_pair[1].y};
                 float ssum = 0.0f, ssq = 0.0f;
-                float o_row[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int m = c_row0 + r;
-                    const float o_new = tanh_fast(fmaf(a16[r], d2l, acc[r]) + cv);
-                    fit_part[r] = fmaf(wrv, o_new, fit_part[r]);
-                    // Statistics over the live rows. Pad columns (col >= O)
-                    // need no mask: their c, d2last and [U;D2] row are 0, so
-                    // o_new = tanh_fast(0) = +0 exactly, and their sums are
-                    // never stored. Row 0 starts the sums: 0 + o and
-                    // fma(o, o, 0) give the same bits (tanh_fast never
-                    // returns -0) but cost an op each.
-                    const bool in = kFull || m < live;
+                    const bool in = kFull || c_row0 + r < live;
                     if (r == 0) {
-                        ssum = in ? o_new : 0.0f;
-                        ssq = in ? o_new * o_new : 0.0f;
+                        ssum = in ? o_row[r] : 0.0f;
+                        ssq = in ? o_row[r] * o_row[r] : 0.0f;
                     } else if (in) {
-                        // o_new is a product ((e - 1) · rcp): without this the
+                        // o is a product ((e - 1) · rcp): without this the
                         // unmasked body contracts it into the add as one fma
                         // (one rounding instead of two), and the sums change bits
 #pragma clang fp contract(off)
-                        ssum += o_new;
-                        ssq = fmaf(o_new, o_new, ssq);
+                        ssum += o_row[r];
+                        ssq = fmaf(o_row[r], o_row[r], ssq);
                     }
-                    o_row[r] = o_new;
                 }
                 // quantize, normalize and store the rows in pairs: one packed
                 // conversion serves two rows (same values as row by row)
 #pragma unroll
-                for (int r = 0; r < 4; r += 2) {
-                    const bf16x2 ob = f2b_pair(o_row[r], o_row[r + 1]);
+                for (int q = 0; q < 2; ++q) {
+                    const bf16x2 ob = f2b_pair(o_pair[q]);
                     const floatx2 of = b2f_pair(ob);
-                    const bf16x2 on = f2b_pair((of.x - mv) * iv, (of.y - mv) * iv);
-                    __bf16* po = obs_l + (c_row0 + r) * OPS + col;
-                    __bf16* pn = obsn_l + (c_row0 + r) * OPS + col;
+                    const bf16x2 on = f2b_pair((of - mv) * iv);
+                    __bf16* po = obs_l + (c_row0 + 2 * q) * OPS + col;
+                    __bf16* pn = obsn_l + (c_row0 + 2 * q) * OPS + col;
                     po[0] = ob.x;
                     po[OPS] = ob.y;
                     pn[0] = on.x;
                     pn[OPS] = on.y;
                 }
-                stat_sum[tw] += ssum;
-                stat_sumsq[tw] += ssq;
+                // the column's running sum and sum of squares as one pair:
+                // one packed add, and nothing to pair across tiles
+                {
+                    const floatx2 tile_stat = {ssum, ssq};
+                    stat[tw] += tile_stat;
+                }
 #pragma unroll
                 for (int u = 0; u < kSqPerTile; ++u) {
                     const int a = tw * kSqPerTile + u;
@@ -585,14 +631,15 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     // be bitwise run-to-run reproducible): (1) shuffle-reduce fit_part
     // across the 16 lanes of each row segment, (2) stage per-wave partials
     // in LDS, (3) one thread per member sums the waves in fixed order.
+    float fit_row[4] = {fit_part[0].x, fit_part[0].y, fit_part[1].x, fit_part[1].y};
 #pragma unroll
     for (int off = 8; off > 0; off >>= 1) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) fit_part[r] += __shfl_down(fit_part[r], off, 16);
+        for (int r = 0; r < 4; ++r) fit_row[r] += __shfl_down(fit_row[r], off, 16);
     }
     if ((lane & 15) == 0) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) wave_fit[wave * 16 + c_row0 + r] = fit_part[r];
+        for (int r = 0; r < 4; ++r) wave_fit[wave * 16 + c_row0 + r] = fit_row[r];
     }
     if (l32 == 31 && my_member < live) actf_l[my_member * AF + A_MAX] = actsq_total;
     __syncthreads();
@@ -610,7 +657,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     float* stats = args.obs_stats_out + (int64_t)blockIdx.x * 2 * O;
 #pragma unroll
     for (int tw = 0; tw < kTilesPerWave; ++tw) {
-        float ss = stat_sum[tw], sq = stat_sumsq[tw];
+        float ss = stat[tw].x, sq = stat[tw].y;
         ss += __shfl_down(ss, 32, 64);
         ss += __shfl_down(ss, 16, 64);
         sq += __shfl_down(sq, 32, 64);
