@@ -34,6 +34,8 @@ torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, 
                                   int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
                                   int64_t member_offset, int64_t policy_hidden, int64_t health_index,
                                   double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf);
+std::string rollout_kernel_name(int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t policy_hidden,
+                                bool terminating);
 void bump_seed(torch::Tensor seed_buf);
 void cma_update_c(torch::Tensor C, torch::Tensor Y, torch::Tensor w, torch::Tensor pc, torch::Tensor hs_f,
                   torch::Tensor wsum, double c1, double cmu, double cc);
@@ -80,13 +82,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("seed_buf") = c10::optional<torch::Tensor>());
     m.def("rollout_terminating", &ea::rollout_terminating,
           "K10+K11 with early termination: an episode ends after the step whose bf16 o'[health_index] leaves "
-          "[healthy_lo, healthy_hi]; episode lengths go to steps_out (general v6 kernel at every geometry)",
+          "[healthy_lo, healthy_hi]; episode lengths go to steps_out (v7 for the linear policy at the Humanoid "
+          "geometry, the general v6 kernel elsewhere)",
           pybind11::arg("params"), pybind11::arg("env_blob"), pybind11::arg("obs_stats_out"),
           pybind11::arg("steps_out"), pybind11::arg("obs_dim"), pybind11::arg("act_dim"), pybind11::arg("rank"),
           pybind11::arg("steps"), pybind11::arg("alive_bonus"), pybind11::arg("act_cost"),
           pybind11::arg("init_seed"), pybind11::arg("member_offset"), pybind11::arg("policy_hidden"),
           pybind11::arg("health_index"), pybind11::arg("healthy_lo"), pybind11::arg("healthy_hi"),
           pybind11::arg("seed_buf") = c10::optional<torch::Tensor>());
+    m.def("rollout_kernel_name", &ea::rollout_kernel_name,
+          "which rollout kernel the dispatcher picks, \"v7\", \"m7\" or \"v6\" (host only; reads "
+          "EVOTORCH_AMD_ROLLOUT_V6 on every call)",
+          pybind11::arg("obs_dim"), pybind11::arg("act_dim"), pybind11::arg("rank"), pybind11::arg("policy_hidden"),
+          pybind11::arg("terminating"));
     m.def("bump_seed", &ea::bump_seed,
           "advance a device splitmix64 seed chain by one step (hipGraph-safe episode seeds)");
     m.def("cma_update_c", &ea::cma_update_c,

@@ -2,10 +2,11 @@
 // through the synthetic vectorized environment, one kernel launch per
 // generation (SURVEY.md §3.4 — the VecGymNE hot loop, collapsed).
 //
-// This file holds the dispatcher `rollout_linear` — with `prepare_rollout`
-// the one place that validates, fills RolloutArgs, picks a kernel and sums
-// the obs-stat partials — its early-terminating sibling
-// `rollout_terminating`, and v6, the general kernel (any geometry, linear
+// This file holds the dispatcher `rollout_linear` — with `prepare_rollout`,
+// `select_rollout_kernel` and `launch_selected` the one place that
+// validates, fills RolloutArgs, picks a kernel and sums the obs-stat
+// partials — its early-terminating sibling `rollout_terminating`, the
+// kernel-name query, and v6, the general kernel (any geometry, linear
 // or MLP policy). The Humanoid-geometry kernels live in rollout_v7.hip (linear,
 // MFMA) and rollout_m7.hip (MLP-64); shared helpers in rollout_common.h.
 //
@@ -53,6 +54,7 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <cstdlib>
+#include <string>
 
 #include "philox.h"
 #include "reduce.h"
@@ -542,6 +544,29 @@ static int v6_members_per_block(int O, int A, int R, int H) {
     return members;
 }
 
+// The one kernel selection, for both entry points and the name query. v7
+// (MFMA, linear) and m7 (MLP-64) serve the Humanoid geometry; v7 also
+// terminates, m7 does not. v6 covers every other geometry and policy width,
+// terminating MLP-64, and everything when EVOTORCH_AMD_ROLLOUT_V6 is set.
+// Read on every call: tests change it within a process.
+enum class RolloutKernel { v6, v7, m7 };
+
+static RolloutKernel select_rollout_kernel(int64_t O, int64_t A, int64_t R, int64_t H, bool terminating) {
+    const bool humanoid = R == 16 && O == 376 && A == 17 && !getenv("EVOTORCH_AMD_ROLLOUT_V6");
+    if (humanoid && H == 0) return RolloutKernel::v7;
+    if (humanoid && H == 64 && !terminating) return RolloutKernel::m7;
+    return RolloutKernel::v6;
+}
+
+std::string rollout_kernel_name(int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t policy_hidden,
+                                bool terminating) {
+    switch (select_rollout_kernel(obs_dim, act_dim, rank, policy_hidden, terminating)) {
+        case RolloutKernel::v7: return "v7";
+        case RolloutKernel::m7: return "m7";
+        default: return "v6";
+    }
+}
+
 // A validated rollout call: the checked operands turned into kernel
 // arguments (all but obs_stats_out, which each entry point sizes for the
 // kernel it picks) and the fitness tensor the kernel writes.
@@ -592,21 +617,14 @@ static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Ten
     return call;
 }
 
-torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
-                             int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
-                             double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
-                             c10::optional<torch::Tensor> seed_buf) {
-    RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
-                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf);
+// Picks the kernel of a validated call, sizes the obs-stat partials for it,
+// launches, and adds the summed partials to obs_stats_out.
+template <bool kTerm>
+static void launch_selected(RolloutCall& call, const torch::Tensor& params, torch::Tensor& obs_stats_out) {
     RolloutArgs& args = call.args;
     const int n = call.n, O = call.O, A = call.A, R = call.R, H = call.H;
-
-    // v7 (MFMA, linear) and m7 (MLP-64) serve the Humanoid geometry; v6
-    // covers every other geometry and policy width, and that geometry too
-    // when EVOTORCH_AMD_ROLLOUT_V6 is set. Read on every call: tests change
-    // it within a process.
-    const bool humanoid = R == 16 && O == 376 && A == 17 && !getenv("EVOTORCH_AMD_ROLLOUT_V6");
-    const bool use_v7 = humanoid && H == 0, use_m7 = humanoid && H == 64;
+    const RolloutKernel kernel = select_rollout_kernel(O, A, R, H, kTerm);
+    const bool use_v7 = kernel == RolloutKernel::v7, use_m7 = kernel == RolloutKernel::m7;
     const int members = use_v7 ? kV7MembersPerBlock : use_m7 ? kM7MembersPerBlock : v6_members_per_block(O, A, R, H);
     const int n_blocks = (n + members - 1) / members;
     // obs-stat partials: one row per block (v7, m7) or per (block, member)
@@ -617,22 +635,32 @@ torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch
 
     auto stream = at::cuda::getCurrentCUDAStream();
     if (use_v7) {
-        launch_rollout_v7(args, n, stream);
+        launch_rollout_v7(args, n, stream, kTerm);
     } else if (use_m7) {
         launch_rollout_m7(args, n, stream);
     } else if (members == 2) {
-        launch_rollout_v6<8, 2, false>(args, n_blocks, v6_layout(O, A, R, H, 2).bytes, stream);
+        launch_rollout_v6<8, 2, kTerm>(args, n_blocks, v6_layout(O, A, R, H, 2).bytes, stream);
     } else {
-        launch_rollout_v6<8, 1, false>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
+        launch_rollout_v6<8, 1, kTerm>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
     }
     obs_stats_out.add_(stat_partials.sum(0));
+}
+
+torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
+                             int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
+                             double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
+                             c10::optional<torch::Tensor> seed_buf) {
+    RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
+                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf);
+    launch_selected<false>(call, params, obs_stats_out);
     return call.fitness;
 }
 
 // rollout_linear with early episode termination: member m is done after the
 // step whose bf16(o'[health_index]) leaves [healthy_lo, healthy_hi], and its
-// length goes to steps_out[m]. Always the terminating v6 kernel, at every
-// geometry (v7 and m7 do not terminate).
+// length goes to steps_out[m]. The terminating v7 for the linear policy at
+// the Humanoid geometry, the terminating v6 everywhere else (m7 does not
+// terminate).
 torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                                   torch::Tensor steps_out, int64_t obs_dim, int64_t act_dim, int64_t rank,
                                   int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
@@ -641,7 +669,7 @@ torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, 
     RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
                                        act_cost, init_seed, member_offset, policy_hidden, seed_buf);
     RolloutArgs& args = call.args;
-    const int n = call.n, O = call.O, A = call.A, R = call.R, H = call.H;
+    const int n = call.n, O = call.O;
     check_operand_as(steps_out, "steps_out", params, at::ScalarType::Int, n);
     TORCH_CHECK(health_index >= 0 && health_index < O, "health_index must be in [0, ", O, "), got ", health_index);
     // written so that a NaN bound fails it too
@@ -652,18 +680,7 @@ torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, 
     args.healthy_hi = (float)healthy_hi;
     args.steps_out = steps_out.data_ptr<int>();
 
-    const int members = v6_members_per_block(O, A, R, H);
-    const int n_blocks = (n + members - 1) / members;
-    auto stat_partials = torch::zeros({(int64_t)n_blocks * members, 2 * (int64_t)O}, params.options());
-    args.obs_stats_out = stat_partials.data_ptr<float>();
-
-    auto stream = at::cuda::getCurrentCUDAStream();
-    if (members == 2) {
-        launch_rollout_v6<8, 2, true>(args, n_blocks, v6_layout(O, A, R, H, 2).bytes, stream);
-    } else {
-        launch_rollout_v6<8, 1, true>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
-    }
-    obs_stats_out.add_(stat_partials.sum(0));
+    launch_selected<true>(call, params, obs_stats_out);
     return call.fitness;
 }
 

@@ -80,7 +80,7 @@ struct RolloutArgs {
     unsigned long long init_seed;
     const unsigned long long* seed_ptr;  // device episode seed (hipGraph-safe); overrides init_seed
     int hidden;               // policy hidden width, 0 = linear policy
-    // early termination (terminating v6 only; the other kernels ignore these):
+    // early termination (the kTerm instantiations of v6 and v7; the other kernels ignore these):
     // a member is done after the step whose bf16(o'[health_index]) leaves
     // [healthy_lo, healthy_hi] (NaN counts as outside)
     int health_index;
@@ -102,8 +102,10 @@ constexpr int kV7MembersPerBlock = 16;
 constexpr int kM7MembersPerBlock = 2;
 
 // Launch entry points of rollout_v7.hip and rollout_m7.hip (Humanoid
-// geometry only; args.obs_stats_out holds one row per block).
-void launch_rollout_v7(const RolloutArgs& args, int n, hipStream_t stream);
+// geometry only; args.obs_stats_out holds one row per block). v7 with
+// `terminating` runs its early-termination instantiation, which reads the
+// health fields of args and writes args.steps_out.
+void launch_rollout_v7(const RolloutArgs& args, int n, hipStream_t stream, bool terminating);
 void launch_rollout_m7(const RolloutArgs& args, int n, hipStream_t stream);
 
 }  // namespace ea

@@ -69,6 +69,11 @@
 // the masked body. A live member's instruction sequence is the same in
 // both.
 //
+// rollout_v7_kernel<O, A, true> adds early episode termination for
+// `rollout_terminating`: the masked body with an alive bit per member slot
+// in place of "slot < live" (protocol at the episode loop). The fixed-length
+// instantiation carries none of it.
+//
 // Every sum keeps the order it had before the transposing reduction, so
 // results are bit-identical to the full-width version; and a member's
 // arithmetic never depends on its slot (half-wave, wave or block):
@@ -247,16 +252,20 @@ struct V7Layout {
     static constexpr int wave_fit = istd + OP * 4;          // float [kWaves][16] fitness partials
     static constexpr int d2last = wave_fit + kWaves * 16 * 4;  // float [OP] D2_T row A-1 (rank-1 epilogue term)
     static constexpr int ud = d2last + OP * 4;              // bf16 [OP][KU] k-major GEMM2 B
-    static constexpr int bytes = ud + OP * KU * 2;
+    static constexpr int alive = ud + OP * KU * 2;          // unsigned: bit m = member slot m still runs (kTerm only)
+    static constexpr int bytes = alive + 16;
     static_assert(bytes <= 160 * 1024, "v7 LDS footprint exceeds the 160 KB of a gfx950 workgroup");
-    static_assert(actf % 16 == 0 && ud % 16 == 0 && v % 16 == 0, "misaligned LDS region");
+    static_assert(actf % 16 == 0 && ud % 16 == 0 && v % 16 == 0 && alive % 4 == 0, "misaligned LDS region");
     // the policy phase reads a lane's obsn chunk as 8-byte words
     static_assert(obsn % 8 == 0 && (OPS * 2) % 8 == 0 && (OP / 32) % 4 == 0, "misaligned policy obs chunk");
 };
 
 // All guards constant-fold: a runtime-guarded W-load was measured to
 // demote w_frag to scratch memory.
-template <int O, int A>
+// kTerm adds early episode termination (see the alive-mask protocol at the
+// episode loop); everything it needs sits behind `if constexpr (kTerm)`, and
+// a live member runs the same arithmetic sequence in both instantiations.
+template <int O, int A, bool kTerm>
 __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_kernel(RolloutArgs args) {
     using L = V7Layout<O, A>;
     constexpr int kWaves = L::kWaves, kM = L::kM, OP = L::OP, OPS = L::OPS, KS = L::KS, KU = L::KU, AF = L::AF;
@@ -286,6 +295,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     float* wave_fit = reinterpret_cast<float*>(lds7 + L::wave_fit);
     float* d2last_l = reinterpret_cast<float*>(lds7 + L::d2last);
     __bf16* ud_l = reinterpret_cast<__bf16*>(lds7 + L::ud);
+    [[maybe_unused]] unsigned* alive_l = reinterpret_cast<unsigned*>(lds7 + L::alive);
 
     const EnvBlob env(args.env_blob, O, A, R);
     const long AO = (long)A * O;
@@ -303,6 +313,10 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     }
     for (int j = tid; j < 16 * KS; j += kThreads) hact_l[j] = f2b(0.0f);
     for (int j = tid; j < kM * AF; j += kThreads) actf_l[j] = 0.0f;
+    // alive mask: the bits of the live slots; an empty slot's bit is never set
+    if constexpr (kTerm) {
+        if (tid == 0) *alive_l = (1u << live) - 1u;
+    }
 
     // GEMM1 B (V) in LDS (only wave 0 reads it — registers on every wave
     // would blow the VGPR budget and demote w_frag to scratch).
@@ -366,6 +380,10 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
         tail_lane ? args.params[(long)(base_member + my_member) * (AO + A) + AO + my_act] : 0.0f;
     __bf16* my_hact = hact_l + my_member * KS + ((my_act < 16) ? (16 + my_act) : 32);
     float* my_actf = actf_l + my_member * AF + my_act;
+    // kTerm: the lane's epilogue column of tile tw is health_index when this
+    // equals 16 * tw (one compare per tile; at most four lanes of one wave,
+    // one per 16-lane row group, ever match)
+    [[maybe_unused]] const int health_rel = args.health_index - (wave * kTilesPerWave * 16 + c_col);
 
     // ---- initial observations (philox stream per global member) -------------
     for (int j = tid; j < kM * OPS; j += kThreads) obs_l[j] = f2b(0.0f);
@@ -413,6 +431,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     floatx2 fit_part[2] = {};                  // member rows (lane>>4)*4 + {0,1}, {2,3} of GEMM2
     float actsq_total = 0.0f;                  // my_member's Σa² (lane 31 of the half-wave publishes it)
     floatx2 stat[kTilesPerWave] = {};          // (sum, sumsq) per owned obs column
+    [[maybe_unused]] int len = 0;              // kTerm: my_member's episode length (lane 31 publishes it)
 
     // the 16 rows of an MFMA A/D fragment are exactly the block's member slots
     static_assert(kM == 16, "GEMM1/GEMM2 fragments address member rows 0..15 unguarded");
@@ -423,9 +442,38 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     // multiple of kM), without the per-member guards; and the masked body
     // for the last, partial block. A live member runs the same instruction
     // sequence in both, so its results do not depend on which one it is in.
+    //
+    // Termination (kTerm) runs the masked body alone, with "slot < live"
+    // replaced by the slot's bit of the alive mask (the bits of slots >= live
+    // are never set, so the one mask serves both purposes). The mask is one
+    // LDS word. Every thread reads it at the top of a step and moves it to a
+    // scalar register, so the member tests of the step test a scalar and the
+    // exit is block-uniform. The bits are cleared in the GEMM2 epilogue by the
+    // lanes that own column health_index, with an integer atomicAnd (order-
+    // independent, deterministic). The read comes after the end-of-step
+    // barrier (the staging barriers for step 0) and before the mid-step
+    // barrier; the next clear comes after the mid-step barrier and before the
+    // end-of-step one: no race and no extra barrier. From the step after its
+    // death a member's fit_part, statistics, Σa² and length stay as they are
+    // (selects and skipped adds, never a zero multiplier: a dead row's later
+    // observations are whatever the closed loop makes of them). Its rows of
+    // obs, obsn and hact keep being computed, which no live member sees: row
+    // m of an MFMA result depends on row m of A alone, and the policy phase
+    // reads a member's own obsn row only.
     auto episode = [&](auto full) __attribute__((always_inline)) {
     constexpr bool kFull = decltype(full)::value;
+    static_assert(!(kTerm && kFull), "the terminating kernel runs the masked body");
     for (int t = 0; t < args.steps; ++t) {
+        [[maybe_unused]] unsigned alive = 0;       // scalar: this step's alive mask
+        [[maybe_unused]] unsigned rows_alive = 0;  // bit r: GEMM2 row c_row0 + r runs
+        [[maybe_unused]] bool member_on = true;    // my_member runs
+        if constexpr (kTerm) {
+            alive = __builtin_amdgcn_readfirstlane(*alive_l);
+            if (alive == 0) break;
+            rows_alive = alive >> c_row0;
+            member_on = (alive >> my_member) & 1u;
+            len += member_on;
+        }
         // ===== GEMM1 (wave 0): h = obs @ Vᵀ, before the wave's policy share
         // (not overlapped with it, see the header) =====
         floatx4 h_acc = {0.f, 0.f, 0.f, 0.f};
@@ -451,7 +499,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
             float acc[A_MAX];
 #pragma unroll
             for (int a = 0; a < A_MAX; ++a) acc[a] = 0.0f;  // for the masked body's dead members only
-            if (kFull || my_member < live) {
+            if (kFull || (kTerm ? member_on : my_member < live)) {
                 // the lane's chunk as 8-byte reads (ds_read_b64), two column pairs each
                 const bf16x4* on = reinterpret_cast<const bf16x4*>(obsn_l + my_member * OPS + l32 * kChunk);
 #pragma unroll
@@ -567,7 +615,14 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 for (int q = 0; q < 2; ++q) {
                     const floatx2 accq = {acc[2 * q], acc[2 * q + 1]};
                     o_pair[q] = tanh_fast_pair(__builtin_elementwise_fma(a16[q], d2l, accq) + cv);
-                    fit_part[q] = __builtin_elementwise_fma(wrv, o_pair[q], fit_part[q]);
+                    const floatx2 fit_next = __builtin_elementwise_fma(wrv, o_pair[q], fit_part[q]);
+                    if constexpr (kTerm) {
+                        // a dead row keeps the sum it died with
+                        fit_part[q].x = ((rows_alive >> (2 * q)) & 1u) ? fit_next.x : fit_part[q].x;
+                        fit_part[q].y = ((rows_alive >> (2 * q + 1)) & 1u) ? fit_next.y : fit_part[q].y;
+                    } else {
+                        fit_part[q] = fit_next;
+                    }
                 }
                 // Statistics over the live rows, one chain in row order per
                 // column. Pad columns (col >= O) need no mask: their c, d2last
@@ -579,7 +634,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 float ssum = 0.0f, ssq = 0.0f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const bool in = kFull || c_row0 + r < live;
+                    const bool in = kFull || (kTerm ? ((rows_alive >> r) & 1u) != 0 : c_row0 + r < live);
                     if (r == 0) {
                         ssum = in ? o_row[r] : 0.0f;
                         ssq = in ? o_row[r] * o_row[r] : 0.0f;
@@ -594,6 +649,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 }
                 // quantize, normalize and store the rows in pairs: one packed
                 // conversion serves two rows (same values as row by row)
+                [[maybe_unused]] floatx2 health[2];
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const bf16x2 ob = f2b_pair(o_pair[q]);
@@ -605,6 +661,22 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                     po[OPS] = ob.y;
                     pn[0] = on.x;
                     pn[OPS] = on.y;
+                    if constexpr (kTerm) health[q] = of;
+                }
+                if constexpr (kTerm) {
+                    // Done after this step: the bf16 value the policy would
+                    // see next is outside the healthy range (a NaN is
+                    // outside). Only the lanes whose column is health_index
+                    // get here, the other waves branch over it.
+                    if (health_rel == 16 * tw) {
+                        const float h4[4] = {health[0].x, health[0].y, health[1].x, health[1].y};
+                        unsigned dead = 0;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (!(args.healthy_lo <= h4[r] && h4[r] <= args.healthy_hi)) dead |= 1u << r;
+                        }
+                        if (dead != 0) atomicAnd(alive_l, ~(dead << c_row0));
+                    }
                 }
                 // the column's running sum and sum of squares as one pair:
                 // one packed add, and nothing to pair across tiles
@@ -618,13 +690,22 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                     if (a < A_MAX) sq = fmaf(av[a / 4][a % 4], av[a / 4][a % 4], sq);
                 }
             }
-            actsq_total += sq;
+            if constexpr (kTerm) {
+                // a dead member's row still holds its last actions
+                if (member_on) actsq_total += sq;
+            } else {
+                actsq_total += sq;
+            }
         }
         __syncthreads();
     }
     };
-    if (live == kM) episode(std::true_type{});
-    else episode(std::false_type{});
+    if constexpr (kTerm) {
+        episode(std::false_type{});
+    } else {
+        if (live == kM) episode(std::true_type{});
+        else episode(std::false_type{});
+    }
 
     // ---- wrap-up ----
     // Deterministic fitness reduction (no float atomics — the kernel must
@@ -641,14 +722,25 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
 #pragma unroll
         for (int r = 0; r < 4; ++r) wave_fit[wave * 16 + c_row0 + r] = fit_row[r];
     }
-    if (l32 == 31 && my_member < live) actf_l[my_member * AF + A_MAX] = actsq_total;
+    if (l32 == 31 && my_member < live) {
+        actf_l[my_member * AF + A_MAX] = actsq_total;
+        if constexpr (kTerm) {
+            // the length rides beside Σa² (its bits in a float slot)
+            static_assert(AF >= A_MAX + 2, "no free actf slot for the episode length");
+            actf_l[my_member * AF + A_MAX + 1] = __builtin_bit_cast(float, len);
+        }
+    }
     __syncthreads();
     if (tid < live) {
         float total = 0.0f;
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) total += wave_fit[w * 16 + tid];
+        // the alive bonus is paid per step survived
+        int steps_m = args.steps;
+        if constexpr (kTerm) steps_m = __builtin_bit_cast(int, actf_l[tid * AF + A_MAX + 1]);
         args.fitness_out[base_member + tid] =
-            total + args.alive_bonus * (float)args.steps - args.act_cost * actf_l[tid * AF + A_MAX] / (float)A;
+            total + args.alive_bonus * (float)steps_m - args.act_cost * actf_l[tid * AF + A_MAX] / (float)A;
+        if constexpr (kTerm) args.steps_out[base_member + tid] = steps_m;
     }
     // per-block stat slice: the four 16-lane groups of a wave share each
     // col (they hold different member rows), so reduce across them with
@@ -670,19 +762,31 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     }
 }
 
-void launch_rollout_v7(const RolloutArgs& args, int n, hipStream_t stream) {
-    constexpr int O_T = 376, A_T = 17;
+template <int O_T, int A_T, bool kTerm>
+static void launch_v7(const RolloutArgs& args, int n, hipStream_t stream) {
     using L = V7Layout<O_T, A_T>;
     static_assert(L::kM == kV7MembersPerBlock, "the dispatcher sizes the stat partials by kV7MembersPerBlock");
-    TORCH_CHECK(args.obs_dim == O_T && args.act_dim == A_T && args.rank == 16 && args.hidden == 0,
-                "rollout v7 is instantiated for the linear policy at the Humanoid geometry (obs 376, act 17, rank 16)");
     static bool attr_set = false;
     if (!attr_set) {
-        allow_max_dynamic_lds(reinterpret_cast<const void*>(&rollout_v7_kernel<O_T, A_T>));
+        allow_max_dynamic_lds(reinterpret_cast<const void*>(&rollout_v7_kernel<O_T, A_T, kTerm>));
         attr_set = true;
     }
     const int blocks = (n + L::kM - 1) / L::kM;
-    hipLaunchKernelGGL((rollout_v7_kernel<O_T, A_T>), dim3(blocks), dim3(64 * L::kWaves), L::bytes, stream, args);
+    hipLaunchKernelGGL((rollout_v7_kernel<O_T, A_T, kTerm>), dim3(blocks), dim3(64 * L::kWaves), L::bytes, stream,
+                       args);
+}
+
+void launch_rollout_v7(const RolloutArgs& args, int n, hipStream_t stream, bool terminating) {
+    constexpr int O_T = 376, A_T = 17;
+    TORCH_CHECK(args.obs_dim == O_T && args.act_dim == A_T && args.rank == 16 && args.hidden == 0,
+                "rollout v7 is instantiated for the linear policy at the Humanoid geometry (obs 376, act 17, rank 16)");
+    if (terminating) {
+        TORCH_CHECK(args.steps_out != nullptr && args.health_index >= 0 && args.health_index < O_T,
+                    "terminating rollout v7 needs steps_out and a health_index in [0, ", O_T, ")");
+        launch_v7<O_T, A_T, true>(args, n, stream);
+    } else {
+        launch_v7<O_T, A_T, false>(args, n, stream);
+    }
 }
 
 }  // namespace ea
