@@ -22,7 +22,7 @@ __all__ = ["SyntheticRolloutProblem"]
 
 
 class SyntheticRolloutProblem(Problem):
-    _NOT_CLONED = Problem._NOT_CLONED + ("_env_blob_state",)
+    _NOT_CLONED = Problem._NOT_CLONED + ("_env_blob_state", "_env_image_state")
 
     def __init__(
         self,
@@ -148,6 +148,22 @@ class SyntheticRolloutProblem(Problem):
         mean, std = self._norm_mean_std()
         return spec.env_blob(mean, std, device=device)
 
+    def _env_image(self, mod, blob: torch.Tensor) -> Optional[torch.Tensor]:
+        """The v7 rollout kernel's prepacked environment
+        (`_C.rollout_env_image_v7`), built once per device: the environment's
+        matrices never change after construction, and the image does not
+        depend on the blob's (mean, std) tail. None where v7 does not run;
+        the other kernels stage the blob themselves."""
+        spec = self._spec
+        kernel = mod.rollout_kernel_name(spec.obs_dim, spec.act_dim, spec.rank, spec.policy_hidden, spec.terminates)
+        if kernel != "v7":
+            return None
+        image = getattr(self, "_env_image_state", None)
+        if image is None or image.device != blob.device:
+            image = mod.rollout_env_image_v7(blob, spec.obs_dim, spec.act_dim, spec.rank)
+            self._env_image_state = image
+        return image
+
     def _default_mean_std(self, device):
         O = self._spec.obs_dim
         return (
@@ -190,6 +206,7 @@ class SyntheticRolloutProblem(Problem):
 
             mod = ops.hip_required()
             blob = self._packed_env_blob(values)
+            env_image = self._env_image(mod, blob)
             obs_stats = torch.zeros(2 * spec.obs_dim, dtype=torch.float32, device=values.device)
             if seed_buf is not None:
                 mod.bump_seed(seed_buf)  # fresh episode seed per replay, on device
@@ -213,6 +230,7 @@ class SyntheticRolloutProblem(Problem):
                     spec.healthy_range[0],
                     spec.healthy_range[1],
                     seed_buf,
+                    env_image,
                 )
                 count = lengths.sum()  # stays on the device: no host sync, capturable
             else:
@@ -230,6 +248,7 @@ class SyntheticRolloutProblem(Problem):
                     member_offset,
                     spec.policy_hidden,
                     seed_buf,
+                    env_image,
                 )
                 lengths = None
                 count = float(n) * spec.episode_length

@@ -28,12 +28,14 @@ void adam_step_graphsafe(torch::Tensor step_out, torch::Tensor grad, torch::Tens
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
-                             c10::optional<torch::Tensor> seed_buf);
+                             c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image);
+torch::Tensor rollout_env_image_v7(torch::Tensor env_blob, int64_t obs_dim, int64_t act_dim, int64_t rank);
 torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                                   torch::Tensor steps_out, int64_t obs_dim, int64_t act_dim, int64_t rank,
                                   int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
                                   int64_t member_offset, int64_t policy_hidden, int64_t health_index,
-                                  double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf);
+                                  double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf,
+                                  c10::optional<torch::Tensor> env_image);
 std::string rollout_kernel_name(int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t policy_hidden,
                                 bool terminating);
 void bump_seed(torch::Tensor seed_buf);
@@ -79,7 +81,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("obs_dim"), pybind11::arg("act_dim"), pybind11::arg("rank"), pybind11::arg("steps"),
           pybind11::arg("alive_bonus"), pybind11::arg("act_cost"), pybind11::arg("init_seed"),
           pybind11::arg("member_offset"), pybind11::arg("policy_hidden") = 0,
-          pybind11::arg("seed_buf") = c10::optional<torch::Tensor>());
+          pybind11::arg("seed_buf") = c10::optional<torch::Tensor>(),
+          pybind11::arg("env_image") = c10::optional<torch::Tensor>());
+    m.def("rollout_env_image_v7", &ea::rollout_env_image_v7,
+          "the v7 rollout kernel's prepacked environment (uint8): the constant range of its LDS layout for this env "
+          "blob, independent of the blob's (mean, std) tail; pass it as env_image (Humanoid geometry only)",
+          pybind11::arg("env_blob"), pybind11::arg("obs_dim"), pybind11::arg("act_dim"), pybind11::arg("rank"));
     m.def("rollout_terminating", &ea::rollout_terminating,
           "K10+K11 with early termination: an episode ends after the step whose bf16 o'[health_index] leaves "
           "[healthy_lo, healthy_hi]; episode lengths go to steps_out (v7 for the linear policy at the Humanoid "
@@ -89,7 +96,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("steps"), pybind11::arg("alive_bonus"), pybind11::arg("act_cost"),
           pybind11::arg("init_seed"), pybind11::arg("member_offset"), pybind11::arg("policy_hidden"),
           pybind11::arg("health_index"), pybind11::arg("healthy_lo"), pybind11::arg("healthy_hi"),
-          pybind11::arg("seed_buf") = c10::optional<torch::Tensor>());
+          pybind11::arg("seed_buf") = c10::optional<torch::Tensor>(),
+          pybind11::arg("env_image") = c10::optional<torch::Tensor>());
     m.def("rollout_kernel_name", &ea::rollout_kernel_name,
           "which rollout kernel the dispatcher picks, \"v7\", \"m7\" or \"v6\" (host only; reads "
           "EVOTORCH_AMD_ROLLOUT_V6 on every call)",

@@ -580,7 +580,8 @@ static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Ten
                                    const torch::Tensor& obs_stats_out, int64_t obs_dim, int64_t act_dim, int64_t rank,
                                    int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
                                    int64_t member_offset, int64_t policy_hidden,
-                                   const c10::optional<torch::Tensor>& seed_buf) {
+                                   const c10::optional<torch::Tensor>& seed_buf,
+                                   const c10::optional<torch::Tensor>& env_image) {
     const unsigned long long* seed_ptr = seed_buf.has_value() ? device_i64_scalar(*seed_buf, "seed_buf") : nullptr;
     check_primary(params, "params", 2);
     TORCH_CHECK(params.scalar_type() == at::ScalarType::Float, "params must be fp32");
@@ -594,6 +595,11 @@ static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Ten
     // the sum of the EnvBlob layout in rollout_common.h
     check_operand(env_blob, "env_blob", params, (2 * (int64_t)R + A + 4) * O);
     check_operand(obs_stats_out, "obs_stats_out", params, 2 * (int64_t)O);
+    // v7's prepacked environment (rollout_env_image_v7); the other kernels ignore it
+    if (env_image.has_value()) {
+        check_operand_as(*env_image, "env_image", params, at::ScalarType::Byte, rollout_v7_env_image_bytes());
+        TORCH_CHECK(reinterpret_cast<uintptr_t>(env_image->data_ptr()) % 16 == 0, "env_image must be 16-byte aligned");
+    }
 
     RolloutCall call;
     call.n = n; call.O = O; call.A = A; call.R = R; call.H = H;
@@ -614,6 +620,7 @@ static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Ten
     args.health_index = 0;
     args.healthy_lo = args.healthy_hi = 0.0f;
     args.steps_out = nullptr;
+    args.env_image = env_image.has_value() ? env_image->data_ptr<uint8_t>() : nullptr;
     return call;
 }
 
@@ -628,9 +635,13 @@ static void launch_selected(RolloutCall& call, const torch::Tensor& params, torc
     const int members = use_v7 ? kV7MembersPerBlock : use_m7 ? kM7MembersPerBlock : v6_members_per_block(O, A, R, H);
     const int n_blocks = (n + members - 1) / members;
     // obs-stat partials: one row per block (v7, m7) or per (block, member)
-    // (v6). The shapes fix the order of the torch reduction below.
+    // (v6). The shapes fix the order of the torch reduction below. Every
+    // block of v7 and m7 stores all 2·O columns of its row in its wrap-up,
+    // whatever its live members, so their partials need no fill; v6 writes
+    // the rows of live members only and keeps the zeros.
     const int64_t stat_rows = (use_v7 || use_m7) ? n_blocks : (int64_t)n_blocks * members;
-    auto stat_partials = torch::zeros({stat_rows, 2 * (int64_t)O}, params.options());
+    auto stat_partials = (use_v7 || use_m7) ? torch::empty({stat_rows, 2 * (int64_t)O}, params.options())
+                                            : torch::zeros({stat_rows, 2 * (int64_t)O}, params.options());
     args.obs_stats_out = stat_partials.data_ptr<float>();
 
     auto stream = at::cuda::getCurrentCUDAStream();
@@ -649,11 +660,29 @@ static void launch_selected(RolloutCall& call, const torch::Tensor& params, torc
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
-                             c10::optional<torch::Tensor> seed_buf) {
+                             c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image) {
     RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
-                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf);
+                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf, env_image);
     launch_selected<false>(call, params, obs_stats_out);
     return call.fitness;
+}
+
+// The bytes of v7's environment image (the constant range of its LDS layout:
+// V, c, wr, d2last and [U;D2], converted and padded as the kernel stages
+// them) for an env blob. It depends on the environment's matrices alone, not
+// on the (mean, std) tail of the blob: build it once per environment and pass
+// it to rollout_linear / rollout_terminating as `env_image`.
+torch::Tensor rollout_env_image_v7(torch::Tensor env_blob, int64_t obs_dim, int64_t act_dim, int64_t rank) {
+    check_primary(env_blob, "env_blob", 1);
+    TORCH_CHECK(env_blob.scalar_type() == at::ScalarType::Float, "env_blob must be fp32");
+    TORCH_CHECK(obs_dim == 376 && act_dim == 17 && rank == 16,
+                "rollout v7 exists for the Humanoid geometry only (obs 376, act 17, rank 16)");
+    TORCH_CHECK(env_blob.numel() == (2 * rank + act_dim + 4) * obs_dim, "env_blob must have ",
+                (2 * rank + act_dim + 4) * obs_dim, " elements, got ", env_blob.numel());
+    auto image = torch::empty({rollout_v7_env_image_bytes()}, env_blob.options().dtype(torch::kUInt8));
+    launch_rollout_v7_env_image(env_blob.data_ptr<float>(), image.data_ptr<uint8_t>(),
+                                at::cuda::getCurrentCUDAStream());
+    return image;
 }
 
 // rollout_linear with early episode termination: member m is done after the
@@ -665,9 +694,10 @@ torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, 
                                   torch::Tensor steps_out, int64_t obs_dim, int64_t act_dim, int64_t rank,
                                   int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
                                   int64_t member_offset, int64_t policy_hidden, int64_t health_index,
-                                  double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf) {
+                                  double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf,
+                                  c10::optional<torch::Tensor> env_image) {
     RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
-                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf);
+                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf, env_image);
     RolloutArgs& args = call.args;
     const int n = call.n, O = call.O;
     check_operand_as(steps_out, "steps_out", params, at::ScalarType::Int, n);

@@ -86,6 +86,9 @@ struct RolloutArgs {
     int health_index;
     float healthy_lo, healthy_hi;
     int* steps_out;           // [n_members] episode lengths
+    // v7 only (v6 and m7 ignore it): the environment's constant LDS range as
+    // rollout_env_image_v7 wrote it, 16-byte aligned; null = stage it from env_blob
+    const unsigned char* env_image = nullptr;
 };
 
 // env_blob layout (fp32, SyntheticEnvSpec.env_blob): V [R][O] · U_T [R][O] ·
@@ -107,5 +110,11 @@ constexpr int kM7MembersPerBlock = 2;
 // health fields of args and writes args.steps_out.
 void launch_rollout_v7(const RolloutArgs& args, int n, hipStream_t stream, bool terminating);
 void launch_rollout_m7(const RolloutArgs& args, int n, hipStream_t stream);
+
+// The bytes of v7's prepacked environment image (the constant range of its
+// LDS layout) and the kernel that writes them from an env blob; Humanoid
+// geometry only.
+int64_t rollout_v7_env_image_bytes();
+void launch_rollout_v7_env_image(const float* env_blob, unsigned char* image, hipStream_t stream);
 
 }  // namespace ea

@@ -16,9 +16,17 @@
 //
 // Blocks: ONE 8-wave block of 16 members per CU (4-wave blocks of 8
 // members, two per CU, measured neutral or worse and were dropped).
-// All MFMA operands live in LDS: V (GEMM1 B),
-// [U;D2] k-major (GEMM2 B) — register fragments for them would push the
-// kernel past 256 VGPRs and demote the policy weights to scratch.
+// The MFMA operands are staged in LDS: V (GEMM1 B, read by wave 0 every
+// step: registers for it on every wave would push the kernel past 256
+// VGPRs and demote the policy weights to scratch) and [U;D2] k-major
+// (GEMM2 B). A wave's own three GEMM2 B fragments are constant over the
+// episode and are read into 12 registers once, before the loop (243 of 256
+// VGPRs in the loop; an earlier, fatter kernel could not afford them).
+//
+// The environment part of LDS (V, c, wr, d2last, [U;D2]) depends on the
+// environment alone. rollout_env_image_v7 writes those bytes once per
+// problem; a launch that is given the image copies it in 16-byte words
+// instead of converting 17 K values from fp32 in each of its blocks.
 //
 // Policy phase (act = clamp(W·obsn + b), no shared operand — not
 // MFMA-shaped): per-member weights stay in REGISTERS, one 32-lane
@@ -243,22 +251,81 @@ struct V7Layout {
     static constexpr int obs = 0;                           // bf16 [kM][OPS] raw (quantized) obs
     static constexpr int obsn = obs + kM * OPS * 2;         // bf16 [kM][OPS] normalized obs
     static constexpr int hact = obsn + kM * OPS * 2;        // bf16 [16][KS]: k<16 h, k=16..31 act[0..16), slot 32 = act[16]
-    static constexpr int v = hact + 16 * KS * 2;            // bf16 [16][OPS] V (GEMM1 B-operand)
-    static constexpr int actf = v + 16 * OPS * 2;           // float [kM][AF] fp32 actions of the step; slot A: Σa² at wrap-up
-    static constexpr int c = actf + kM * AF * 4;            // float [OP]
-    static constexpr int wr = c + OP * 4;                   // float [OP]
-    static constexpr int mean = wr + OP * 4;                // float [OP]
+    static constexpr int actf = hact + 16 * KS * 2;         // float [kM][AF] fp32 actions of the step; slot A: Σa² at wrap-up
+    static constexpr int mean = actf + kM * AF * 4;         // float [OP]
     static constexpr int istd = mean + OP * 4;              // float [OP]
     static constexpr int wave_fit = istd + OP * 4;          // float [kWaves][16] fitness partials
-    static constexpr int d2last = wave_fit + kWaves * 16 * 4;  // float [OP] D2_T row A-1 (rank-1 epilogue term)
+    static constexpr int alive = wave_fit + kWaves * 16 * 4;  // unsigned: bit m = member slot m still runs (kTerm only)
+    // The environment image [env_begin, env_end): every region that depends
+    // on the environment's matrices alone, not on (mean, std), the weights or
+    // the episode. rollout_env_image_v7 writes these bytes once per problem
+    // and a launch that is given them copies the range in 16-byte words.
+    static constexpr int env_begin = alive + 16;
+    static constexpr int v = env_begin;                     // bf16 [16][OPS] V (GEMM1 B-operand)
+    static constexpr int c = v + 16 * OPS * 2;              // float [OP]
+    static constexpr int wr = c + OP * 4;                   // float [OP]
+    static constexpr int d2last = wr + OP * 4;              // float [OP] D2_T row A-1 (rank-1 epilogue term)
     static constexpr int ud = d2last + OP * 4;              // bf16 [OP][KU] k-major GEMM2 B
-    static constexpr int alive = ud + OP * KU * 2;          // unsigned: bit m = member slot m still runs (kTerm only)
-    static constexpr int bytes = alive + 16;
+    static constexpr int env_end = ud + OP * KU * 2;
+    static constexpr int env_bytes = env_end - env_begin;
+    static constexpr int bytes = env_end;
     static_assert(bytes <= 160 * 1024, "v7 LDS footprint exceeds the 160 KB of a gfx950 workgroup");
     static_assert(actf % 16 == 0 && ud % 16 == 0 && v % 16 == 0 && alive % 4 == 0, "misaligned LDS region");
+    static_assert(env_begin % 16 == 0 && env_bytes % 16 == 0, "the environment image is copied in 16-byte words");
     // the policy phase reads a lane's obsn chunk as 8-byte words
     static_assert(obsn % 8 == 0 && (OPS * 2) % 8 == 0 && (OP / 32) % 4 == 0, "misaligned policy obs chunk");
 };
+
+// Writes the environment image of V7Layout from the fp32 env blob: `img` is
+// byte env_begin of the layout, in LDS for a rollout launch without a
+// prepacked image and in global memory for rollout_v7_env_image_kernel, so
+// the two hold the same bytes by construction. Thread `tid` of `n_threads`;
+// every byte of the range is written exactly once.
+template <int O, int A>
+__device__ __forceinline__ void stage_env_image_v7(unsigned char* img, const EnvBlob& env, int tid, int n_threads) {
+    using L = V7Layout<O, A>;
+    constexpr int OP = L::OP, OPS = L::OPS, KU = L::KU;
+    constexpr int R = 16;
+    __bf16* v_l = reinterpret_cast<__bf16*>(img + (L::v - L::env_begin));
+    float* c_l = reinterpret_cast<float*>(img + (L::c - L::env_begin));
+    float* wr_l = reinterpret_cast<float*>(img + (L::wr - L::env_begin));
+    float* d2last_l = reinterpret_cast<float*>(img + (L::d2last - L::env_begin));
+    __bf16* ud_l = reinterpret_cast<__bf16*>(img + (L::ud - L::env_begin));
+
+    // vectors (pads: c = 0, wr = 0, d2last = 0)
+    for (int j = tid; j < OP; j += n_threads) {
+        const bool in = j < O;
+        c_l[j] = in ? env.c[j] : 0.0f;
+        wr_l[j] = in ? env.wr[j] : 0.0f;
+        // act[A-1]'s D2 row is applied as a rank-1 epilogue term (bf16-
+        // quantized like the mfma operands) so the GEMM K stays 32
+        d2last_l[j] = in ? b2f(f2b(env.D2_T[(long)(A - 1) * O + j])) : 0.0f;
+    }
+    // GEMM1 B (V)
+    for (int j = tid; j < 16 * OPS; j += n_threads) {
+        const int r = j / OPS, o = j % OPS;
+        v_l[j] = (r < R && o < O) ? f2b(env.V[(long)r * O + o]) : f2b(0.0f);
+    }
+    // GEMM2 B ([U;D2 rows 0..15]): K = 32 exactly (R=16 h-rows + 16 action
+    // rows; action A-1 is the rank-1 epilogue term), k-major with padded
+    // stride KU.
+    for (int j = tid; j < OP * KU; j += n_threads) {
+        const int o = j / KU, k = j % KU;
+        float v = 0.0f;
+        if (o < O && k < 32) {
+            if (k < R) v = env.U_T[(long)k * O + o];
+            else if (k - R < A - 1) v = env.D2_T[(long)(k - R) * O + o];
+        }
+        ud_l[j] = f2b(v);
+    }
+}
+
+// rollout_env_image_v7: the image in global memory, once per environment.
+template <int O, int A>
+__global__ __launch_bounds__(256) void rollout_v7_env_image_kernel(const float* env_blob, unsigned char* image) {
+    const EnvBlob env(env_blob, O, A, 16);
+    stage_env_image_v7<O, A>(image, env, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
 
 // All guards constant-fold: a runtime-guarded W-load was measured to
 // demote w_frag to scratch memory.
@@ -300,16 +367,28 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     const EnvBlob env(args.env_blob, O, A, R);
     const long AO = (long)A * O;
 
-    // ---- stage vectors (pads: c=0, wr=0, mean=0, istd=0 → obsn pad = 0) ----
+    // ---- stage the environment: V (GEMM1 B, which only wave 0 reads —
+    // registers on every wave would blow the VGPR budget and demote w_frag to
+    // scratch), c, wr, d2last and [U;D2] (GEMM2 B). A prepacked image is the
+    // same bytes, copied in 16-byte words; without one they are converted
+    // from the fp32 blob here. ----
+    if (args.env_image != nullptr) {
+        constexpr int kWords = L::env_bytes / 16;
+        const uint4* src = reinterpret_cast<const uint4*>(args.env_image);
+        uint4* dst = reinterpret_cast<uint4*>(lds7 + L::env_begin);
+#pragma unroll
+        for (int i = 0; i < (kWords + kThreads - 1) / kThreads; ++i) {
+            const int j = tid + i * kThreads;
+            if (j < kWords) dst[j] = src[j];
+        }
+    } else {
+        stage_env_image_v7<O, A>(lds7 + L::env_begin, env, tid, kThreads);
+    }
+    // ---- this generation's (mean, 1/std) (pads: mean=0, istd=0 → obsn pad = 0) ----
     for (int j = tid; j < OP; j += kThreads) {
         const bool in = j < O;
-        c_l[j] = in ? env.c[j] : 0.0f;
-        wr_l[j] = in ? env.wr[j] : 0.0f;
         mean_l[j] = in ? env.mean[j] : 0.0f;
         istd_l[j] = in ? 1.0f / env.std[j] : 0.0f;
-        // act[A-1]'s D2 row is applied as a rank-1 epilogue term (bf16-
-        // quantized like the mfma operands) so the GEMM K stays 32
-        d2last_l[j] = in ? b2f(f2b(env.D2_T[(long)(A - 1) * O + j])) : 0.0f;
     }
     for (int j = tid; j < 16 * KS; j += kThreads) hact_l[j] = f2b(0.0f);
     for (int j = tid; j < kM * AF; j += kThreads) actf_l[j] = 0.0f;
@@ -318,30 +397,10 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
         if (tid == 0) *alive_l = (1u << live) - 1u;
     }
 
-    // GEMM1 B (V) in LDS (only wave 0 reads it — registers on every wave
-    // would blow the VGPR budget and demote w_frag to scratch).
-    for (int j = tid; j < 16 * OPS; j += kThreads) {
-        const int r = j / OPS, o = j % OPS;
-        v_l[j] = (r < R && o < O) ? f2b(env.V[(long)r * O + o]) : f2b(0.0f);
-    }
-
     const int g2_row = lane & 15;              // A-frag row (member) for GEMM2/GEMM1
     const int g2_k0 = (lane >> 4) * 8;
     const int c_col = lane & 15;               // C-frag col
     const int c_row0 = (lane >> 4) * 4;        // C-frag first row (member)
-
-    // GEMM2 B ([U;D2 rows 0..15]): K = 32 exactly (R=16 h-rows + 16 action
-    // rows; action A-1 is the rank-1 epilogue term), k-major LDS with
-    // padded stride KU.
-    for (int j = tid; j < OP * KU; j += kThreads) {
-        const int o = j / KU, k = j % KU;
-        float v = 0.0f;
-        if (o < O && k < 32) {
-            if (k < R) v = env.U_T[(long)k * O + o];
-            else if (k - R < A - 1) v = env.D2_T[(long)(k - R) * O + o];
-        }
-        ud_l[j] = f2b(v);
-    }
 
     // ---- per-member policy weights in registers -----------------------------
     // half-wave (32 lanes) per member: member = 2*wave + (lane>>5);
@@ -356,17 +415,32 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
     bf16x2 w_frag[A_MAX][kChunk / 2];
     {
         const float* W = args.params + (long)(base_member + min(my_member, live - 1)) * ((long)A * O + A);
+        // A lane's kChunk floats of a row are contiguous: three 16-byte
+        // loads a row, all 51 independent. (One guarded 4-byte load per
+        // column compiled to an exec-masked region with its own
+        // s_waitcnt vmcnt(0) per column, 136 global round trips in a row.)
+        // A member's rows are only 4-byte aligned (6409 floats per member),
+        // which a global load tolerates; O and the chunk are multiples of 4,
+        // so a word is inside the row or all padding, and a padding word
+        // (the last half-wave lane's columns >= O) reads the row's first
+        // word instead and is replaced by zeros.
+        static_assert(O % 4 == 0 && kChunk % 4 == 0, "a 16-byte word of a weight row straddles the row's end");
+        typedef float floatx4_a4 __attribute__((ext_vector_type(4), aligned(4)));
         const int cbase = l32 * kChunk;
 #pragma unroll
         for (int a = 0; a < A_MAX; ++a) {
             const float* Wa = W + (long)(a < 16 ? (a ^ perm) : a) * O;
 #pragma unroll
-            for (int p = 0; p < kChunk / 2; ++p) {
-                const int k0 = cbase + 2 * p;
-                bf16x2 w2;
-                w2.x = (k0 < O) ? f2b(Wa[k0]) : f2b(0.0f);
-                w2.y = (k0 + 1 < O) ? f2b(Wa[k0 + 1]) : f2b(0.0f);
-                w_frag[a][p] = w2;
+            for (int q = 0; q < kChunk / 4; ++q) {
+                const bool in = cbase + 4 * q < O;
+                const floatx4_a4 w4 = *reinterpret_cast<const floatx4_a4*>(in ? Wa + cbase + 4 * q : Wa);
+                bf16x2 lo, hi;
+                lo.x = in ? f2b(w4.x) : f2b(0.0f);
+                lo.y = in ? f2b(w4.y) : f2b(0.0f);
+                hi.x = in ? f2b(w4.z) : f2b(0.0f);
+                hi.y = in ? f2b(w4.w) : f2b(0.0f);
+                w_frag[a][2 * q] = lo;
+                w_frag[a][2 * q + 1] = hi;
             }
         }
     }
@@ -425,6 +499,13 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
         wr_r[tw] = wr_l[col];
         mean_r[tw] = mean_l[col];
         istd_r[tw] = istd_l[col];
+    }
+    // ... and the wave's three GEMM2 B fragments ([U;D2] columns of its tiles)
+    bf16x8 ud_r[kTilesPerWave];
+#pragma unroll
+    for (int tw = 0; tw < kTilesPerWave; ++tw) {
+        const int col = (wave * kTilesPerWave + tw) * 16 + c_col;
+        ud_r[tw] = *reinterpret_cast<const bf16x8*>(ud_l + col * KU + g2_k0);
     }
 
     // ---- episode state in registers ----
@@ -598,8 +679,7 @@ __global__ __launch_bounds__((64 * V7Layout<O, A>::kWaves), 1) void rollout_v7_k
                 }
                 const int col = (wave * kTilesPerWave + tw) * 16 + c_col;
                 floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-                const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(ud_l + col * KU + g2_k0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, ud_r[tw], acc, 0, 0, 0);
                 const floatx2 d2l = {d2last_r[tw], d2last_r[tw]};
                 const floatx2 cv = {c_r[tw], c_r[tw]};
                 const floatx2 wrv = {wr_r[tw], wr_r[tw]};
@@ -787,6 +867,16 @@ void launch_rollout_v7(const RolloutArgs& args, int n, hipStream_t stream, bool 
     } else {
         launch_v7<O_T, A_T, false>(args, n, stream);
     }
+}
+
+int64_t rollout_v7_env_image_bytes() { return V7Layout<376, 17>::env_bytes; }
+
+void launch_rollout_v7_env_image(const float* env_blob, unsigned char* image, hipStream_t stream) {
+    constexpr int O_T = 376, A_T = 17;
+    // one thread per element of the largest region
+    constexpr int kThreads = 256, kBlocks = (V7Layout<O_T, A_T>::OP * V7Layout<O_T, A_T>::KU + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL((rollout_v7_env_image_kernel<O_T, A_T>), dim3(kBlocks), dim3(kThreads), 0, stream, env_blob,
+                       image);
 }
 
 }  // namespace ea
