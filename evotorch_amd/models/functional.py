@@ -5,18 +5,68 @@ Reference parity: /root/reference/src/evotorch/neuroevolution/net/
 functional.py (ModuleExpectingFlatParameters :46, make_functional_module
 :203) and the vmapped population forward of net/vecrl.py:1261-1265.
 
-MI355X note: the population-batched forward of Linear-family policies is
-GEMM-shaped work (K10 in SURVEY.md §2.9). `torch.func.vmap` over
-`functional_call` lowers population-batched Linear layers to rocBLAS
-batched GEMMs (bmm); the fully-fused LDS-resident path for linear policies
-lives in evotorch_amd/ops/hip/rollout.hip.
+MI355X note: the population-batched forward of a dense stack (nn.Linear
+layers with Tanh / ReLU between them) is a GEMV chain per member and runs
+as ONE kernel launch, `ops.population_forward` (K13,
+ops/hip/policy_forward.hip). Every other module goes through
+`torch.func.vmap` over `functional_call`, which lowers population-batched
+layers to library calls. The whole-episode fused path for the synthetic
+environment lives in evotorch_amd/ops/hip/rollout.hip.
 """
 
 import copy
+from typing import Optional, Tuple
+
 import torch
 from torch import nn
 
-__all__ = ["ModuleExpectingFlatParameters", "make_functional_module"]
+from .. import ops
+from .multilayered import MultiLayered
+
+__all__ = ["ModuleExpectingFlatParameters", "dense_stack_description", "make_functional_module"]
+
+
+def dense_stack_description(net: nn.Module) -> Optional[Tuple[list, list, bool]]:
+    """(widths, activation codes, has_bias) when `net` is a dense stack that
+    `ops.population_forward` computes, else None.
+
+    A dense stack is exactly an `nn.Linear`, or an `nn.Sequential` /
+    `MultiLayered` whose children are exactly `nn.Linear`, `nn.Tanh` and
+    `nn.ReLU` instances (subclasses may override forward and are not
+    recognised): 1 to 4 Linear layers that chain, widths up to 1024, all
+    with a bias or none, at most one activation after each Linear and none
+    before the first, no buffers, no module used twice."""
+    if type(net) is nn.Linear:
+        layers = [net]
+    elif type(net) in (nn.Sequential, MultiLayered):
+        layers = list(net)
+    else:
+        return None
+    if len(set(map(id, layers))) != len(layers) or next(net.buffers(), None) is not None:
+        return None
+    codes = {nn.Tanh: ops.POPULATION_FORWARD_ACTIVATIONS.index("tanh"), nn.ReLU: ops.POPULATION_FORWARD_ACTIVATIONS.index("relu")}
+    widths, activations, biases = [], [], []
+    after_linear = False
+    for layer in layers:
+        if type(layer) is nn.Linear:
+            if widths and widths[-1] != layer.in_features:
+                return None
+            if not widths:
+                widths.append(layer.in_features)
+            widths.append(layer.out_features)
+            activations.append(ops.POPULATION_FORWARD_ACTIVATIONS.index("identity"))
+            biases.append(layer.bias is not None)
+            after_linear = True
+        elif type(layer) in codes and after_linear:
+            activations[-1] = codes[type(layer)]
+            after_linear = False
+        else:
+            return None
+    if not 1 <= len(activations) <= ops.POPULATION_FORWARD_MAX_LAYERS or len(set(biases)) != 1:
+        return None
+    if not all(1 <= w <= ops.POPULATION_FORWARD_MAX_WIDTH for w in widths):
+        return None
+    return widths, activations, biases[0]
 
 
 class ModuleExpectingFlatParameters:
@@ -24,7 +74,8 @@ class ModuleExpectingFlatParameters:
 
     With a 2-D `flat_params` (popsize × L) the call is vmapped across the
     population: `f(params_2d, batched_inputs)` evaluates every member's
-    network in one batched pass.
+    network in one batched pass. Dense stacks (`dense_stack_description`)
+    with fp32 ROCm parameters run that pass as one HIP kernel launch.
     """
 
     def __init__(self, net: nn.Module, *, disable_autograd_tracking: bool = True):
@@ -32,6 +83,7 @@ class ModuleExpectingFlatParameters:
         self._param_shapes = [(name, p.shape, p.numel()) for name, p in self._net.named_parameters()]
         self._length = sum(n for _, _, n in self._param_shapes)
         self._buffers = dict(self._net.named_buffers())
+        self._dense_stack = dense_stack_description(self._net)
         if disable_autograd_tracking:
             for p in self._net.parameters():
                 p.requires_grad_(False)
@@ -52,10 +104,29 @@ class ModuleExpectingFlatParameters:
         params = self.parameter_dict(flat)
         return torch.func.functional_call(self._net, {**params, **self._buffers}, inputs)
 
+    def _takes_kernel(self, flat_params: torch.Tensor, inputs: tuple) -> bool:
+        """Whether this 2-D call is `ops.population_forward`'s: a dense
+        stack, fp32 ROCm parameters, one fp32 (n, D0) input beside them, no
+        gradient asked for, and the HIP path switched on."""
+        if self._dense_stack is None or len(inputs) != 1 or not isinstance(inputs[0], torch.Tensor):
+            return False
+        x = inputs[0]
+        if flat_params.device.type != "cuda" or flat_params.dtype != torch.float32:
+            return False
+        if x.device != flat_params.device or x.dtype != torch.float32:
+            return False
+        if x.shape != (flat_params.shape[0], self._dense_stack[0][0]) or flat_params.shape[1] != self._length:
+            return False
+        if torch.is_grad_enabled() and (flat_params.requires_grad or x.requires_grad):
+            return False  # the kernel has no backward
+        return ops.hip_for(flat_params) is not None
+
     def __call__(self, flat_params: torch.Tensor, *inputs):
         if flat_params.ndim == 1:
             return self._single(flat_params, *inputs)
         if flat_params.ndim == 2:
+            if self._takes_kernel(flat_params, inputs):
+                return ops.population_forward(flat_params, inputs[0], *self._dense_stack)
             return torch.func.vmap(self._single)(flat_params, *inputs)
         raise ValueError(f"flat_params must be 1-D or 2-D, got ndim={flat_params.ndim}")
 

@@ -6,8 +6,9 @@ Reference parity: the `Policy` class of
 (vmapped call :1261-1265, masked state reset via reset_tensors :866).
 
 The parameters tensor may be 1-D (single member) or 2-D (population);
-2-D parameters run the whole population per step as a batched forward
-(rocBLAS batched GEMMs for Linear stacks — K10 in SURVEY.md §2.9).
+2-D parameters run the whole population per step as a batched forward:
+one `ops.population_forward` launch (K13) for Linear/Tanh/ReLU stacks on a
+ROCm device, the vmapped `functional_call` for every other module.
 """
 
 from typing import Any, Optional, Union

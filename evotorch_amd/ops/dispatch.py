@@ -15,7 +15,8 @@ snes_gradients, K4 clipup_step / adam_step, K4b gaussian_clipup_update, K12
 obsnorm_pack / obsnorm_merge, K5 cma_update_c, K5b potrf_tile,
 K7 pareto_ranks / domination_counts, K9 mapelites_assign (routed from
 algorithms/mapelites.py), K10+K11 rollout_linear (called from
-neuroevolution/synthetic.py).
+neuroevolution/synthetic.py), K13 population_forward (routed from
+models/functional.py).
 
 The launchers check every operand (ops/hip/check.h): dense, on the primary
 tensor's device, of its dtype and of exactly the length the kernel reads.
@@ -52,6 +53,10 @@ __all__ = [
     "pareto_ranks",
     "domination_counts",
     "cma_update_c_",
+    "population_forward",
+    "POPULATION_FORWARD_MAX_LAYERS",
+    "POPULATION_FORWARD_MAX_WIDTH",
+    "POPULATION_FORWARD_ACTIVATIONS",
 ]
 
 
@@ -495,6 +500,58 @@ def fused_adam_step_(
     vhat = v32 / (1.0 - beta2**step_count)
     param_step_out.copy_((stepsize * mhat / (vhat.sqrt() + epsilon)).to(param_step_out.dtype))
     return param_step_out
+
+
+# ============================================================================
+# K13 — population-batched forward of a dense policy stack
+# ============================================================================
+
+POPULATION_FORWARD_MAX_LAYERS = 4  # kMaxLayers of policy_forward.hip
+POPULATION_FORWARD_MAX_WIDTH = 1024  # kMaxWidth
+POPULATION_FORWARD_ACTIVATIONS = ("identity", "tanh", "relu")  # the activation codes, by position
+
+
+def population_forward(params: torch.Tensor, obs: torch.Tensor, widths, activations, has_bias: bool) -> torch.Tensor:
+    """Every member's own dense network applied to its own observation:
+    `params` is (n, L), `obs` (n, widths[0]), the result (n, widths[-1]).
+
+    Row m of `params` is member m's flat vector in `named_parameters()`
+    order of a stack of `nn.Linear`: W_0 (widths[1] x widths[0], row-major),
+    b_0 (widths[1], if `has_bias`), W_1, ... Layer i is followed by
+    `activations[i]`, a code indexing POPULATION_FORWARD_ACTIVATIONS.
+
+    fp32 ROCm tensors take ONE kernel launch (ops/hip/policy_forward.hip),
+    on the current stream and without a host sync (hipGraph-capturable); a
+    member's output bits do not depend on the rest of the population. CPU
+    tensors, other dtypes, and ROCm tensors under `eager_on_gpu()` run the
+    eager chain below, the kernel's oracle."""
+    widths = [int(w) for w in widths]
+    activations = [int(a) for a in activations]
+    n_layers = len(widths) - 1
+    if not 1 <= n_layers <= POPULATION_FORWARD_MAX_LAYERS or len(activations) != n_layers:
+        raise ValueError(
+            f"expected 1 to {POPULATION_FORWARD_MAX_LAYERS} layers with one activation each, "
+            f"got widths={widths}, activations={activations}"
+        )
+    if params.ndim != 2 or obs.shape != (params.shape[0], widths[0]):
+        raise ValueError(f"expected params (n, L) and obs (n, {widths[0]}), got {tuple(params.shape)} and {tuple(obs.shape)}")
+    mod = hip_for(params) if params.dtype == torch.float32 else None
+    if mod is not None:
+        return mod.population_mlp_forward(params.contiguous(), *_dense(params, obs), widths, activations, bool(has_bias))
+    n, x, offset = params.shape[0], obs, 0
+    for k, j, act in zip(widths[:-1], widths[1:], activations):
+        W = params[:, offset : offset + j * k].reshape(n, j, k)
+        offset += j * k
+        x = torch.einsum("nk,njk->nj", x, W)
+        if has_bias:
+            x = x + params[:, offset : offset + j]
+            offset += j
+        name = POPULATION_FORWARD_ACTIVATIONS[act]
+        if name != "identity":
+            x = getattr(torch, name)(x)
+    if offset != params.shape[1]:
+        raise ValueError(f"this stack takes {offset} parameters per member, got {params.shape[1]}")
+    return x
 
 
 # ============================================================================

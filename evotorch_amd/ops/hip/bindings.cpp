@@ -25,6 +25,8 @@ void adam_step(torch::Tensor step_out, torch::Tensor grad, torch::Tensor m, torc
                double stepsize, double beta1, double beta2, double epsilon);
 void adam_step_graphsafe(torch::Tensor step_out, torch::Tensor grad, torch::Tensor m, torch::Tensor v,
                          torch::Tensor t_buf, double stepsize, double beta1, double beta2, double epsilon);
+torch::Tensor population_mlp_forward(torch::Tensor params, torch::Tensor obs, std::vector<int64_t> widths,
+                                     std::vector<int64_t> activations, bool has_bias);
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
@@ -75,6 +77,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("adam_step", &ea::adam_step, "K4: fused Adam ascent step");
     m.def("adam_step_graphsafe", &ea::adam_step_graphsafe,
           "K4 (hipGraph-safe): Adam with device-side step counter");
+    m.def("population_mlp_forward", &ea::population_mlp_forward,
+          "K13: forward of a dense policy stack (1-4 Linear layers; activation codes 0 identity, 1 tanh, 2 ReLU) for "
+          "every member's own flat parameter vector; fp32, returns [n, widths[-1]]",
+          py::arg("params"), py::arg("obs"), py::arg("widths"), py::arg("activations"), py::arg("has_bias"));
     m.def("rollout_linear", &ea::rollout_linear,
           "K10+K11: fused policy episode rollout (linear or MLP-H, synthetic env)",
           pybind11::arg("params"), pybind11::arg("env_blob"), pybind11::arg("obs_stats_out"),
