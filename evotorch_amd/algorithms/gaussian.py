@@ -173,6 +173,12 @@ class GaussianSearchAlgorithm(SearchAlgorithm, SinglePopulationAlgorithmMixin):
 
 
     def _step_distributed(self):
+        # where the one-launch update will run, it applies the gradients'
+        # count divisors itself: the distribution hands over raw sums and
+        # the multipliers (see SeparableGaussian._divide_grad). A user's
+        # after-grad hook keeps seeing divided gradients.
+        if self._fused_update_applies() and len(self.problem.after_grad_hook) == 0:
+            self._distribution._deferred_grad_scales = {}
         fetched = self.problem.sample_and_compute_gradients(
             self._distribution,
             self._popsize,
@@ -246,22 +252,13 @@ class GaussianSearchAlgorithm(SearchAlgorithm, SinglePopulationAlgorithmMixin):
         ClipUp, scalar stdev bounds, L within the kernel's bound. Returns
         False, having done nothing, for anything else; `_update_distribution`
         then runs its chain, which gives the same bits."""
+        if not self._fused_update_applies():
+            return False
         dist = self._distribution
         opt = self._optimizer
-        if type(dist) not in (SeparableGaussian, SymmetricSeparableGaussian) or type(opt) is not ClipUp:
-            return False
-        if self._stdev_bound_scalars is None:
-            return False
         mu, sigma = dist.parameters["mu"], dist.parameters["sigma"]
         velocity = opt._velocity
-        if (
-            mu.numel() > ops.GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH
-            or sigma.dtype != torch.float32
-            or velocity.dtype != torch.float32
-            or velocity.device != mu.device
-            or ops.fused_tail_for(mu) is None
-        ):
-            return False
+        scales = dist._deferred_grad_scales or {}
         stdev_min, stdev_max, stdev_max_change = self._stdev_bound_scalars
         new_mu, new_sigma = ops.gaussian_clipup_update(
             mu,
@@ -276,13 +273,37 @@ class GaussianSearchAlgorithm(SearchAlgorithm, SinglePopulationAlgorithmMixin):
             stdev_min=stdev_min,
             stdev_max=stdev_max,
             stdev_max_change=stdev_max_change,
+            mu_grad_scale=scales.get("mu", 1.0),
+            sigma_grad_scale=scales.get("sigma", 1.0),
         )
         self._distribution = dist.modified_copy(mu=new_mu, sigma=new_sigma)
         return True
 
+    def _fused_update_applies(self) -> bool:
+        dist = self._distribution
+        opt = self._optimizer
+        if type(dist) not in (SeparableGaussian, SymmetricSeparableGaussian) or type(opt) is not ClipUp:
+            return False
+        if self._stdev_bound_scalars is None:
+            return False
+        mu, sigma = dist.parameters["mu"], dist.parameters["sigma"]
+        velocity = opt._velocity
+        return not (
+            mu.numel() > ops.GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH
+            or sigma.dtype != torch.float32
+            or velocity.dtype != torch.float32
+            or velocity.device != mu.device
+            or ops.fused_tail_for(mu) is None
+        )
+
     def _update_distribution(self, gradients: dict):
         if self._update_distribution_fused(gradients):
             return
+        scales = getattr(self._distribution, "_deferred_grad_scales", None)
+        if scales:
+            # raw sums were handed over for the one-launch update, which did
+            # not run after all: the same fp32 multiply, as a launch
+            gradients = {k: (g * scales[k] if k in scales else g) for k, g in gradients.items()}
         controlled = (self._stdev_min is not None) or (self._stdev_max is not None) or (self._stdev_max_change is not None)
         old_sigma = self._distribution.parameters.get("sigma", None) if controlled else None
 

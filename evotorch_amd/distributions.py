@@ -21,6 +21,7 @@ MI355X:
 import math
 from typing import Iterable, Optional, Type, NamedTuple
 
+import numpy as np
 import torch
 
 from .utils import Device, DType, TensorMakerMixin, to_torch_dtype
@@ -314,14 +315,28 @@ class SeparableGaussian(Distribution):
             weights = weights - weights.mean()
         return weights
 
+    # A dict while a consumer has asked to apply the count divisors itself
+    # (`GaussianSearchAlgorithm`, whose one-launch update multiplies inside
+    # the kernel): `_divide_grad` then returns the raw sum and leaves the
+    # multiplier here under the parameter's name.
+    _deferred_grad_scales: Optional[dict] = None
+
+    @staticmethod
+    def _count_scale(count: int) -> float:
+        """What `grad / count` multiplies by: torch divides a tensor by a
+        Python number as a multiply by the fp32 reciprocal."""
+        return float(np.float32(1.0) / np.float32(count))
+
     def _divide_grad(self, param_name: str, grad: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
         option = self._parameters.get(f"divide_{param_name}_grad_by", None)
         if option is None:
             return grad
-        if option == "num_solutions":
-            return grad / weights.shape[0]
-        if option == "num_directions":
-            return grad / (weights.shape[0] // 2)
+        if option in ("num_solutions", "num_directions"):
+            count = weights.shape[0] if option == "num_solutions" else weights.shape[0] // 2
+            if self._deferred_grad_scales is not None and grad.dtype == torch.float32 and count > 0:
+                self._deferred_grad_scales[param_name] = self._count_scale(count)
+                return grad
+            return grad / count
         if option == "total_weight":
             return grad / weights.abs().sum()
         if option == "weight_stdev":

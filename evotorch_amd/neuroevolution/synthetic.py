@@ -207,7 +207,27 @@ class SyntheticRolloutProblem(Problem):
             mod = ops.hip_required()
             blob = self._packed_env_blob(values)
             env_image = self._env_image(mod, blob)
-            obs_stats = torch.zeros(2 * spec.obs_dim, dtype=torch.float32, device=values.device)
+            # With the fused tail, and the batch keeping its evals as a
+            # dense fp32 column nothing is subtracted from, the dispatcher
+            # gets the pair (stats, that column) as plain outputs: it
+            # reduces the obs-stat partials straight into the unwritten
+            # stats (no fill, no add) and the kernel stores the fitnesses
+            # where the batch keeps them (no copy in set_evals).
+            evals = batch._evals
+            fitness_out = None
+            if (
+                ops.fused_tail_for(values) is not None
+                and self._decrease_rewards_by == 0.0
+                and evals.dtype == torch.float32
+                and evals.shape == (n, 1)
+                and evals.device == values.device
+                and evals[:, 0].is_contiguous()
+            ):
+                fitness_out = evals[:, 0]
+                obs_stats = torch.empty(2 * spec.obs_dim, dtype=torch.float32, device=values.device)
+                stats_operand = (obs_stats, fitness_out)
+            else:
+                obs_stats = stats_operand = torch.zeros(2 * spec.obs_dim, dtype=torch.float32, device=values.device)
             if seed_buf is not None:
                 mod.bump_seed(seed_buf)  # fresh episode seed per replay, on device
             if spec.terminates:
@@ -215,7 +235,7 @@ class SyntheticRolloutProblem(Problem):
                 fitness = mod.rollout_terminating(
                     values.contiguous(),
                     blob,
-                    obs_stats,
+                    stats_operand,
                     lengths,
                     spec.obs_dim,
                     spec.act_dim,
@@ -237,7 +257,7 @@ class SyntheticRolloutProblem(Problem):
                 fitness = mod.rollout_linear(
                     values.contiguous(),
                     blob,
-                    obs_stats,
+                    stats_operand,
                     spec.obs_dim,
                     spec.act_dim,
                     spec.rank,
@@ -254,6 +274,7 @@ class SyntheticRolloutProblem(Problem):
                 count = float(n) * spec.episode_length
             triple = (count, obs_stats[: spec.obs_dim], obs_stats[spec.obs_dim :])
         else:
+            fitness_out = None
             mean, std = self._norm_mean_std()
             fitness, triple, lengths = rollout_eager(
                 spec,
@@ -269,7 +290,8 @@ class SyntheticRolloutProblem(Problem):
             # per step survived
             survived = spec.episode_length if lengths is None else lengths.to(fitness.dtype)
             fitness = fitness - self._decrease_rewards_by * survived
-        batch.set_evals(fitness.to(self._eval_dtype))
+        if fitness_out is None:  # else the kernel wrote the batch's own column
+            batch.set_evals(fitness.to(self._eval_dtype))
         if lengths is None:
             self._last_episode_lengths = (n, values.device)  # all episode_length: built when read
             self.last_eval_interaction_count = n * spec.episode_length

@@ -381,6 +381,8 @@ def gaussian_clipup_update(
     stdev_min: Optional[float] = None,
     stdev_max: Optional[float] = None,
     stdev_max_change: Optional[float] = None,
+    mu_grad_scale: float = 1.0,
+    sigma_grad_scale: float = 1.0,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """The distribution update of a separable Gaussian under ClipUp:
     `velocity` takes one ClipUp step along `mu_grad` in place (as
@@ -390,7 +392,13 @@ def gaussian_clipup_update(
 
     fp32 ROCm vectors up to GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH elements take
     ONE kernel launch; anything else runs the chain of launches below. Both
-    give the same bits. No host sync either way (hipGraph-capturable)."""
+    give the same bits. No host sync either way (hipGraph-capturable).
+
+    `mu_grad_scale` / `sigma_grad_scale`: the gradients are
+    ``mu_grad * mu_grad_scale`` and ``sigma_grad * sigma_grad_scale``, each
+    one fp32 multiply done inside the launch: what a separate
+    ``grad * scale`` (or ``grad / number`` with ``scale`` the fp32
+    reciprocal) would hand over, without its launch."""
     mod = fused_tail_for(mu)
     if (
         mod is not None
@@ -409,9 +417,16 @@ def gaussian_clipup_update(
             None if stdev_min is None else float(stdev_min),
             None if stdev_max is None else float(stdev_max),
             None if stdev_max_change is None else float(stdev_max_change),
+            float(mu_grad_scale),
+            float(sigma_grad_scale),
         )
         return new_mu, new_sigma
     from ..utils.misc import modify_tensor
+
+    if mu_grad_scale != 1.0:
+        mu_grad = mu_grad * float(mu_grad_scale)
+    if sigma_grad_scale != 1.0:
+        sigma_grad = sigma_grad * float(sigma_grad_scale)
 
     clipup_step_(velocity, mu_grad, step_size=step_size, max_speed=max_speed, momentum=momentum)
     new_mu = mu + velocity

@@ -15,7 +15,8 @@ std::vector<torch::Tensor> gaussian_clipup_update(torch::Tensor mu, torch::Tenso
                                                   torch::Tensor mu_grad, torch::Tensor sigma_grad, double step_size,
                                                   double momentum, double max_speed, double sigma_lr,
                                                   c10::optional<double> stdev_min, c10::optional<double> stdev_max,
-                                                  c10::optional<double> stdev_max_change);
+                                                  c10::optional<double> stdev_max_change, double mu_grad_scale,
+                                                  double sigma_grad_scale);
 int64_t gaussian_clipup_update_max_length();
 void obsnorm_pack(torch::Tensor count, torch::Tensor sum, torch::Tensor sumsq, double min_variance,
                   torch::Tensor blob, int64_t offset);
@@ -30,14 +31,16 @@ torch::Tensor population_mlp_forward(torch::Tensor params, torch::Tensor obs, st
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
-                             c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image);
+                             c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image,
+                             c10::optional<torch::Tensor> fitness_out, bool overwrite_stats);
 torch::Tensor rollout_env_image_v7(torch::Tensor env_blob, int64_t obs_dim, int64_t act_dim, int64_t rank);
 torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                                   torch::Tensor steps_out, int64_t obs_dim, int64_t act_dim, int64_t rank,
                                   int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
                                   int64_t member_offset, int64_t policy_hidden, int64_t health_index,
                                   double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf,
-                                  c10::optional<torch::Tensor> env_image);
+                                  c10::optional<torch::Tensor> env_image, c10::optional<torch::Tensor> fitness_out,
+                                  bool overwrite_stats);
 std::string rollout_kernel_name(int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t policy_hidden,
                                 bool terminating);
 void bump_seed(torch::Tensor seed_buf);
@@ -67,7 +70,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("mu"), py::arg("sigma"), py::arg("velocity"), py::arg("mu_grad"), py::arg("sigma_grad"),
           py::arg("step_size"), py::arg("momentum"), py::arg("max_speed"), py::arg("sigma_lr"),
           py::arg("stdev_min") = c10::optional<double>(), py::arg("stdev_max") = c10::optional<double>(),
-          py::arg("stdev_max_change") = c10::optional<double>());
+          py::arg("stdev_max_change") = c10::optional<double>(), py::arg("mu_grad_scale") = 1.0,
+          py::arg("sigma_grad_scale") = 1.0);
     m.def("gaussian_clipup_update_max_length", &ea::gaussian_clipup_update_max_length,
           "largest solution length gaussian_clipup_update accepts");
     m.def("obsnorm_pack", &ea::obsnorm_pack,
@@ -81,7 +85,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "K13: forward of a dense policy stack (1-4 Linear layers; activation codes 0 identity, 1 tanh, 2 ReLU) for "
           "every member's own flat parameter vector; fp32, returns [n, widths[-1]]",
           py::arg("params"), py::arg("obs"), py::arg("widths"), py::arg("activations"), py::arg("has_bias"));
-    m.def("rollout_linear", &ea::rollout_linear,
+    // Both rollout entry points take `obs_stats_out` either as one tensor, to
+    // which the summed statistics are ADDED and a fresh fitness tensor is
+    // returned, or as a pair (obs_stats_out, fitness_out) of plain outputs:
+    // the statistics are then reduced straight into the first (no fill, no
+    // add) and the kernels store the fitnesses into the second, which is
+    // returned. Every other operand keeps its place.
+    using OutPair = std::tuple<torch::Tensor, torch::Tensor>;
+    m.def("rollout_linear",
+          [](torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out, int64_t obs_dim,
+             int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
+             int64_t member_offset, int64_t policy_hidden, c10::optional<torch::Tensor> seed_buf,
+             c10::optional<torch::Tensor> env_image) {
+              return ea::rollout_linear(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
+                                        act_cost, init_seed, member_offset, policy_hidden, seed_buf, env_image,
+                                        c10::nullopt, false);
+          },
           "K10+K11: fused policy episode rollout (linear or MLP-H, synthetic env)",
           pybind11::arg("params"), pybind11::arg("env_blob"), pybind11::arg("obs_stats_out"),
           pybind11::arg("obs_dim"), pybind11::arg("act_dim"), pybind11::arg("rank"), pybind11::arg("steps"),
@@ -89,11 +108,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("member_offset"), pybind11::arg("policy_hidden") = 0,
           pybind11::arg("seed_buf") = c10::optional<torch::Tensor>(),
           pybind11::arg("env_image") = c10::optional<torch::Tensor>());
+    m.def("rollout_linear",
+          [](torch::Tensor params, torch::Tensor env_blob, OutPair outputs, int64_t obs_dim, int64_t act_dim,
+             int64_t rank, int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
+             int64_t member_offset, int64_t policy_hidden, c10::optional<torch::Tensor> seed_buf,
+             c10::optional<torch::Tensor> env_image) {
+              return ea::rollout_linear(params, env_blob, std::get<0>(outputs), obs_dim, act_dim, rank, steps,
+                                        alive_bonus, act_cost, init_seed, member_offset, policy_hidden, seed_buf,
+                                        env_image, std::get<1>(outputs), true);
+          },
+          "rollout_linear writing into the pair (obs_stats_out, fitness_out): statistics overwritten, not added; "
+          "fitness_out fp32, dense, exactly n elements, and returned",
+          pybind11::arg("params"), pybind11::arg("env_blob"), pybind11::arg("outputs"), pybind11::arg("obs_dim"),
+          pybind11::arg("act_dim"), pybind11::arg("rank"), pybind11::arg("steps"), pybind11::arg("alive_bonus"),
+          pybind11::arg("act_cost"), pybind11::arg("init_seed"), pybind11::arg("member_offset"),
+          pybind11::arg("policy_hidden") = 0, pybind11::arg("seed_buf") = c10::optional<torch::Tensor>(),
+          pybind11::arg("env_image") = c10::optional<torch::Tensor>());
     m.def("rollout_env_image_v7", &ea::rollout_env_image_v7,
           "the v7 rollout kernel's prepacked environment (uint8): the constant range of its LDS layout for this env "
           "blob, independent of the blob's (mean, std) tail; pass it as env_image (Humanoid geometry only)",
           pybind11::arg("env_blob"), pybind11::arg("obs_dim"), pybind11::arg("act_dim"), pybind11::arg("rank"));
-    m.def("rollout_terminating", &ea::rollout_terminating,
+    m.def("rollout_terminating",
+          [](torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out, torch::Tensor steps_out,
+             int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus, double act_cost,
+             int64_t init_seed, int64_t member_offset, int64_t policy_hidden, int64_t health_index, double healthy_lo,
+             double healthy_hi, c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image) {
+              return ea::rollout_terminating(params, env_blob, obs_stats_out, steps_out, obs_dim, act_dim, rank, steps,
+                                             alive_bonus, act_cost, init_seed, member_offset, policy_hidden,
+                                             health_index, healthy_lo, healthy_hi, seed_buf, env_image, c10::nullopt,
+                                             false);
+          },
           "K10+K11 with early termination: an episode ends after the step whose bf16 o'[health_index] leaves "
           "[healthy_lo, healthy_hi]; episode lengths go to steps_out (v7 for the linear policy at the Humanoid "
           "geometry, the general v6 kernel elsewhere)",
@@ -102,6 +146,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("steps"), pybind11::arg("alive_bonus"), pybind11::arg("act_cost"),
           pybind11::arg("init_seed"), pybind11::arg("member_offset"), pybind11::arg("policy_hidden"),
           pybind11::arg("health_index"), pybind11::arg("healthy_lo"), pybind11::arg("healthy_hi"),
+          pybind11::arg("seed_buf") = c10::optional<torch::Tensor>(),
+          pybind11::arg("env_image") = c10::optional<torch::Tensor>());
+    m.def("rollout_terminating",
+          [](torch::Tensor params, torch::Tensor env_blob, OutPair outputs, torch::Tensor steps_out, int64_t obs_dim,
+             int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
+             int64_t member_offset, int64_t policy_hidden, int64_t health_index, double healthy_lo, double healthy_hi,
+             c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image) {
+              return ea::rollout_terminating(params, env_blob, std::get<0>(outputs), steps_out, obs_dim, act_dim, rank,
+                                             steps, alive_bonus, act_cost, init_seed, member_offset, policy_hidden,
+                                             health_index, healthy_lo, healthy_hi, seed_buf, env_image,
+                                             std::get<1>(outputs), true);
+          },
+          "rollout_terminating writing into the pair (obs_stats_out, fitness_out), as rollout_linear does",
+          pybind11::arg("params"), pybind11::arg("env_blob"), pybind11::arg("outputs"), pybind11::arg("steps_out"),
+          pybind11::arg("obs_dim"), pybind11::arg("act_dim"), pybind11::arg("rank"), pybind11::arg("steps"),
+          pybind11::arg("alive_bonus"), pybind11::arg("act_cost"), pybind11::arg("init_seed"),
+          pybind11::arg("member_offset"), pybind11::arg("policy_hidden"), pybind11::arg("health_index"),
+          pybind11::arg("healthy_lo"), pybind11::arg("healthy_hi"),
           pybind11::arg("seed_buf") = c10::optional<torch::Tensor>(),
           pybind11::arg("env_image") = c10::optional<torch::Tensor>());
     m.def("rollout_kernel_name", &ea::rollout_kernel_name,

@@ -443,17 +443,22 @@ __global__ __launch_bounds__(kUpdateThreads) void gaussian_clipup_update_kernel(
     const float* __restrict__ mu, const float* __restrict__ sigma, float* __restrict__ velocity,
     const float* __restrict__ mu_grad, const float* __restrict__ sigma_grad, float* __restrict__ new_mu,
     float* __restrict__ new_sigma, int n, float step_size, float momentum, float max_speed, float sigma_lr,
-    float stdev_min, float stdev_max, float stdev_max_change, int bounds) {
+    float stdev_min, float stdev_max, float stdev_max_change, int bounds, float mu_grad_scale,
+    float sigma_grad_scale) {
 #pragma clang fp contract(off)
     __shared__ float wave_sums[kUpdateThreads];
     __shared__ float tops[4];
 
-    const float gnorm_sq = clipup_tree_sumsq([&](int i) { return mu_grad[i]; }, n, wave_sums, tops);
+    // the gradients are raw sums times a scale: one rounded multiply before
+    // the first use, as the separate `grad / number` launch rounds it (a
+    // scale of 1 changes no bit)
+    const float gnorm_sq = clipup_tree_sumsq([&](int i) { return mu_grad[i] * mu_grad_scale; }, n, wave_sums, tops);
     const float gnorm = sqrtf(fmaxf(gnorm_sq, 1e-30f));
     const float scale = step_size / gnorm;
     const float vnorm_sq = clipup_tree_sumsq(
         [&](int i) {
-            const float v = fmaf(momentum, velocity[i], mu_grad[i] * scale);
+            const float g = mu_grad[i] * mu_grad_scale;
+            const float v = fmaf(momentum, velocity[i], g * scale);
             velocity[i] = v;
             return v;
         },
@@ -472,7 +477,8 @@ __global__ __launch_bounds__(kUpdateThreads) void gaussian_clipup_update_kernel(
 
         const float s = sigma[i];
         // torch.add(sigma, grad, alpha=lr) is one fma in torch's ROCm build
-        float target = fmaf(sigma_lr, sigma_grad[i], s);
+        const float sg = sigma_grad[i] * sigma_grad_scale;
+        float target = fmaf(sigma_lr, sg, s);
         if (bounds & kHasStdevMaxChange) {
             const float allowed = fabsf(s) * stdev_max_change;
             float lo = s - allowed;
@@ -492,7 +498,8 @@ std::vector<torch::Tensor> gaussian_clipup_update(torch::Tensor mu, torch::Tenso
                                                   torch::Tensor mu_grad, torch::Tensor sigma_grad, double step_size,
                                                   double momentum, double max_speed, double sigma_lr,
                                                   c10::optional<double> stdev_min, c10::optional<double> stdev_max,
-                                                  c10::optional<double> stdev_max_change) {
+                                                  c10::optional<double> stdev_max_change, double mu_grad_scale,
+                                                  double sigma_grad_scale) {
     check_primary(mu, "mu", 1);
     TORCH_CHECK(mu.scalar_type() == torch::kFloat32, "gaussian_clipup_update expects float32, got ", mu.scalar_type());
     const int64_t n = mu.numel();
@@ -512,7 +519,7 @@ std::vector<torch::Tensor> gaussian_clipup_update(torch::Tensor mu, torch::Tenso
                        sigma_grad.data_ptr<float>(), new_mu.data_ptr<float>(), new_sigma.data_ptr<float>(), (int)n,
                        (float)step_size, (float)momentum, (float)max_speed, (float)sigma_lr,
                        (float)stdev_min.value_or(0.0), (float)stdev_max.value_or(0.0),
-                       (float)stdev_max_change.value_or(0.0), bounds);
+                       (float)stdev_max_change.value_or(0.0), bounds, (float)mu_grad_scale, (float)sigma_grad_scale);
     return {new_mu, new_sigma};
 }
 

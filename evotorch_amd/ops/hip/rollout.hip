@@ -581,7 +581,8 @@ static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Ten
                                    int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
                                    int64_t member_offset, int64_t policy_hidden,
                                    const c10::optional<torch::Tensor>& seed_buf,
-                                   const c10::optional<torch::Tensor>& env_image) {
+                                   const c10::optional<torch::Tensor>& env_image,
+                                   const c10::optional<torch::Tensor>& fitness_out) {
     const unsigned long long* seed_ptr = seed_buf.has_value() ? device_i64_scalar(*seed_buf, "seed_buf") : nullptr;
     check_primary(params, "params", 2);
     TORCH_CHECK(params.scalar_type() == at::ScalarType::Float, "params must be fp32");
@@ -601,9 +602,13 @@ static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Ten
         TORCH_CHECK(reinterpret_cast<uintptr_t>(env_image->data_ptr()) % 16 == 0, "env_image must be 16-byte aligned");
     }
 
+    // where the caller keeps the fitnesses: the kernels store them one by
+    // one at unit stride, so a dense fp32 vector of exactly n
+    if (fitness_out.has_value()) check_operand(*fitness_out, "fitness_out", params, n);
+
     RolloutCall call;
     call.n = n; call.O = O; call.A = A; call.R = R; call.H = H;
-    call.fitness = torch::empty({n}, params.options());
+    call.fitness = fitness_out.has_value() ? *fitness_out : torch::empty({n}, params.options());
     RolloutArgs& args = call.args;
     args.params = params.data_ptr<float>();
     args.env_blob = env_blob.data_ptr<float>();
@@ -625,9 +630,12 @@ static RolloutCall prepare_rollout(const torch::Tensor& params, const torch::Ten
 }
 
 // Picks the kernel of a validated call, sizes the obs-stat partials for it,
-// launches, and adds the summed partials to obs_stats_out.
+// launches, and adds the summed partials to obs_stats_out, or with
+// `overwrite_stats` reduces them straight into it (the same reduction, so the
+// bits of zeros + sum, without the fill and the add).
 template <bool kTerm>
-static void launch_selected(RolloutCall& call, const torch::Tensor& params, torch::Tensor& obs_stats_out) {
+static void launch_selected(RolloutCall& call, const torch::Tensor& params, torch::Tensor& obs_stats_out,
+                            bool overwrite_stats) {
     RolloutArgs& args = call.args;
     const int n = call.n, O = call.O, A = call.A, R = call.R, H = call.H;
     const RolloutKernel kernel = select_rollout_kernel(O, A, R, H, kTerm);
@@ -654,16 +662,22 @@ static void launch_selected(RolloutCall& call, const torch::Tensor& params, torc
     } else {
         launch_rollout_v6<8, 1, kTerm>(args, n_blocks, v6_layout(O, A, R, H, 1).bytes, stream);
     }
-    obs_stats_out.add_(stat_partials.sum(0));
+    if (overwrite_stats) {
+        at::sum_out(obs_stats_out, stat_partials, {0});
+    } else {
+        obs_stats_out.add_(stat_partials.sum(0));
+    }
 }
 
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
-                             c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image) {
+                             c10::optional<torch::Tensor> seed_buf, c10::optional<torch::Tensor> env_image,
+                             c10::optional<torch::Tensor> fitness_out, bool overwrite_stats) {
     RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
-                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf, env_image);
-    launch_selected<false>(call, params, obs_stats_out);
+                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf, env_image,
+                                       fitness_out);
+    launch_selected<false>(call, params, obs_stats_out, overwrite_stats);
     return call.fitness;
 }
 
@@ -695,9 +709,11 @@ torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, 
                                   int64_t steps, double alive_bonus, double act_cost, int64_t init_seed,
                                   int64_t member_offset, int64_t policy_hidden, int64_t health_index,
                                   double healthy_lo, double healthy_hi, c10::optional<torch::Tensor> seed_buf,
-                                  c10::optional<torch::Tensor> env_image) {
+                                  c10::optional<torch::Tensor> env_image, c10::optional<torch::Tensor> fitness_out,
+                                  bool overwrite_stats) {
     RolloutCall call = prepare_rollout(params, env_blob, obs_stats_out, obs_dim, act_dim, rank, steps, alive_bonus,
-                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf, env_image);
+                                       act_cost, init_seed, member_offset, policy_hidden, seed_buf, env_image,
+                                       fitness_out);
     RolloutArgs& args = call.args;
     const int n = call.n, O = call.O;
     check_operand_as(steps_out, "steps_out", params, at::ScalarType::Int, n);
@@ -710,7 +726,7 @@ torch::Tensor rollout_terminating(torch::Tensor params, torch::Tensor env_blob, 
     args.healthy_hi = (float)healthy_hi;
     args.steps_out = steps_out.data_ptr<int>();
 
-    launch_selected<true>(call, params, obs_stats_out);
+    launch_selected<true>(call, params, obs_stats_out, overwrite_stats);
     return call.fitness;
 }
 
