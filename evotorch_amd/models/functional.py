@@ -8,7 +8,10 @@ functional.py (ModuleExpectingFlatParameters :46, make_functional_module
 MI355X note: the population-batched forward of a dense stack (nn.Linear
 layers with Tanh / ReLU between them) is a GEMV chain per member and runs
 as ONE kernel launch, `ops.population_forward` (K13,
-ops/hip/policy_forward.hip). Every other module goes through
+ops/hip/policy_forward.hip), and the same stack applied by every member to
+one shared minibatch (`forward_shared`, SupervisedNE's evaluation) is a
+GEMM chain per member on fp32 MFMA, `ops.population_forward_shared` (K14,
+ops/hip/policy_forward_shared.hip). Every other module goes through
 `torch.func.vmap` over `functional_call`, which lowers population-batched
 layers to library calls. The whole-episode fused path for the synthetic
 environment lives in evotorch_amd/ops/hip/rollout.hip.
@@ -84,6 +87,7 @@ class ModuleExpectingFlatParameters:
         self._length = sum(n for _, _, n in self._param_shapes)
         self._buffers = dict(self._net.named_buffers())
         self._dense_stack = dense_stack_description(self._net)
+        self._shared_tile = None  # K14's batch tile for this stack, asked of the extension once
         if disable_autograd_tracking:
             for p in self._net.parameters():
                 p.requires_grad_(False)
@@ -120,6 +124,40 @@ class ModuleExpectingFlatParameters:
         if torch.is_grad_enabled() and (flat_params.requires_grad or x.requires_grad):
             return False  # the kernel has no backward
         return ops.hip_for(flat_params) is not None
+
+    def takes_shared_kernel(self, flat_params: torch.Tensor, x) -> bool:
+        """Whether `forward_shared(flat_params, x)` is
+        `ops.population_forward_shared`'s: a dense stack, 2-D fp32 ROCm
+        parameters, `x` 2-D fp32 of width D0 on the same device, no
+        gradient asked for, the HIP path switched on, and widths narrow
+        enough for the kernel's 32-row batch tiles (wider stacks measured
+        slower than the vmap path)."""
+        if self._dense_stack is None or not isinstance(x, torch.Tensor):
+            return False
+        if flat_params.device.type != "cuda" or flat_params.dtype != torch.float32:
+            return False
+        if x.device != flat_params.device or x.dtype != torch.float32:
+            return False
+        if flat_params.ndim != 2 or flat_params.shape[1] != self._length:
+            return False
+        if x.ndim != 2 or x.shape[1] != self._dense_stack[0][0]:
+            return False
+        if torch.is_grad_enabled() and (flat_params.requires_grad or x.requires_grad):
+            return False  # the kernel has no backward
+        mod = ops.hip_for(flat_params)
+        if mod is None:
+            return False
+        if self._shared_tile is None:
+            self._shared_tile = mod.population_mlp_forward_shared_batch_tile(self._dense_stack[0])
+        return self._shared_tile >= ops.POPULATION_FORWARD_SHARED_MIN_TILE
+
+    def forward_shared(self, flat_params: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """Every member of the 2-D `flat_params` (n, L) applied to the same
+        input batch `x`: (n, B, *out). One `ops.population_forward_shared`
+        launch where `takes_shared_kernel` holds, else vmapped."""
+        if self.takes_shared_kernel(flat_params, x):
+            return ops.population_forward_shared(flat_params, x, *self._dense_stack)
+        return torch.func.vmap(self._single, in_dims=(0, None))(flat_params, x)
 
     def __call__(self, flat_params: torch.Tensor, *inputs):
         if flat_params.ndim == 1:

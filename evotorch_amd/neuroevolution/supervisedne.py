@@ -7,8 +7,10 @@ on the SAME minibatch, so their fitnesses are directly comparable).
 
 MI355X-native evaluation path: instead of looping solutions through one
 network, the whole population is evaluated on the minibatch in a single
-vmapped batched forward (rocBLAS batched GEMMs) when
-`vectorized_eval=True` (default for common_minibatch mode).
+batched forward when `vectorized_eval=True` (default for
+common_minibatch mode): one fp32-MFMA kernel launch for a dense stack on
+a 2-D fp32 ROCm minibatch (`forward_shared`, K14), vmapped (rocBLAS
+batched GEMMs) otherwise.
 """
 
 from typing import Callable, Optional, Union
@@ -17,6 +19,7 @@ import torch
 from torch import nn
 from torch.utils.data import DataLoader, Dataset
 
+from .. import ops
 from ..core import SolutionBatch
 from ..models import make_functional_module
 from .neproblem import NEProblem
@@ -162,6 +165,10 @@ class SupervisedNE(NEProblem):
 
                     if pop_fwd is not None:
                         preds = pop_fwd(params[start:stop], x)
+                        chunk = torch.func.vmap(lambda p: self._loss(p, y))(preds)
+                    elif self._fmodule.takes_shared_kernel(params[start:stop], x):
+                        # dense stack on a 2-D fp32 ROCm minibatch: one K14 launch
+                        preds = ops.population_forward_shared(params[start:stop], x, *self._fmodule._dense_stack)
                         chunk = torch.func.vmap(lambda p: self._loss(p, y))(preds)
                     else:
                         def member_loss(flat):

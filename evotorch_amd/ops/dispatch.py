@@ -15,8 +15,8 @@ snes_gradients, K4 clipup_step / adam_step, K4b gaussian_clipup_update, K12
 obsnorm_pack / obsnorm_merge, K5 cma_update_c, K5b potrf_tile,
 K7 pareto_ranks / domination_counts, K9 mapelites_assign (routed from
 algorithms/mapelites.py), K10+K11 rollout_linear (called from
-neuroevolution/synthetic.py), K13 population_forward (routed from
-models/functional.py).
+neuroevolution/synthetic.py), K13 population_forward and K14
+population_forward_shared (routed from models/functional.py).
 
 The launchers check every operand (ops/hip/check.h): dense, on the primary
 tensor's device, of its dtype and of exactly the length the kernel reads.
@@ -54,9 +54,11 @@ __all__ = [
     "domination_counts",
     "cma_update_c_",
     "population_forward",
+    "population_forward_shared",
     "POPULATION_FORWARD_MAX_LAYERS",
     "POPULATION_FORWARD_MAX_WIDTH",
     "POPULATION_FORWARD_ACTIVATIONS",
+    "POPULATION_FORWARD_SHARED_MIN_TILE",
 ]
 
 
@@ -540,14 +542,7 @@ def population_forward(params: torch.Tensor, obs: torch.Tensor, widths, activati
     member's output bits do not depend on the rest of the population. CPU
     tensors, other dtypes, and ROCm tensors under `eager_on_gpu()` run the
     eager chain below, the kernel's oracle."""
-    widths = [int(w) for w in widths]
-    activations = [int(a) for a in activations]
-    n_layers = len(widths) - 1
-    if not 1 <= n_layers <= POPULATION_FORWARD_MAX_LAYERS or len(activations) != n_layers:
-        raise ValueError(
-            f"expected 1 to {POPULATION_FORWARD_MAX_LAYERS} layers with one activation each, "
-            f"got widths={widths}, activations={activations}"
-        )
+    widths, activations = _stack_description(widths, activations)
     if params.ndim != 2 or obs.shape != (params.shape[0], widths[0]):
         raise ValueError(f"expected params (n, L) and obs (n, {widths[0]}), got {tuple(params.shape)} and {tuple(obs.shape)}")
     mod = hip_for(params) if params.dtype == torch.float32 else None
@@ -567,6 +562,67 @@ def population_forward(params: torch.Tensor, obs: torch.Tensor, widths, activati
     if offset != params.shape[1]:
         raise ValueError(f"this stack takes {offset} parameters per member, got {params.shape[1]}")
     return x
+
+
+def _stack_description(widths, activations):
+    widths = [int(w) for w in widths]
+    activations = [int(a) for a in activations]
+    n_layers = len(widths) - 1
+    if not 1 <= n_layers <= POPULATION_FORWARD_MAX_LAYERS or len(activations) != n_layers:
+        raise ValueError(
+            f"expected 1 to {POPULATION_FORWARD_MAX_LAYERS} layers with one activation each, "
+            f"got widths={widths}, activations={activations}"
+        )
+    return widths, activations
+
+
+# ============================================================================
+# K14 — population-batched forward of a dense stack on one shared minibatch
+# ============================================================================
+
+
+# Routing rule (models/functional.py): a stack goes to K14 when its LDS
+# buffers leave room for batch tiles of at least this many rows. Measured at
+# n = 1024, B = 128 (docs/kernels.md): 64-row tiles 3.1x the vmap path,
+# 32-row tiles 1.05x, 16-row tiles (784 -> 128 -> 10) 0.42x. At B = 32 and at
+# n = 64 the routed stacks win by 3x to 12x; the 16-row stack wins only at
+# small n (4.6x at n = 64, 0.79x at n = 1024, B = 32) and stays unrouted.
+POPULATION_FORWARD_SHARED_MIN_TILE = 32
+
+
+def population_forward_shared(params: torch.Tensor, x: torch.Tensor, widths, activations, has_bias: bool) -> torch.Tensor:
+    """Every member's own dense network applied to the SAME minibatch:
+    `params` is (n, L), `x` (B, widths[0]), the result (n, B, widths[-1]).
+    The stack description and the layout of a `params` row are those of
+    `population_forward`.
+
+    fp32 ROCm tensors take ONE kernel launch on fp32 MFMA
+    (ops/hip/policy_forward_shared.hip), on the current stream and without
+    a host sync (hipGraph-capturable); `out[m, b]` depends bit for bit on
+    `params[m]`, `x[b]` and the stack description only. CPU tensors, other
+    dtypes, and ROCm tensors under `eager_on_gpu()` run the eager chain
+    below, the kernel's oracle."""
+    widths, activations = _stack_description(widths, activations)
+    if params.ndim != 2 or x.ndim != 2 or x.shape[1] != widths[0]:
+        raise ValueError(f"expected params (n, L) and x (B, {widths[0]}), got {tuple(params.shape)} and {tuple(x.shape)}")
+    mod = hip_for(params) if params.dtype == torch.float32 else None
+    if mod is not None:
+        return mod.population_mlp_forward_shared(params.contiguous(), *_dense(params, x), widths, activations, bool(has_bias))
+    expected = sum(j * k + (j if has_bias else 0) for k, j in zip(widths[:-1], widths[1:]))
+    if params.shape[1] != expected:
+        raise ValueError(f"this stack takes {expected} parameters per member, got {params.shape[1]}")
+    n, offset, h = params.shape[0], 0, None
+    for k, j, act in zip(widths[:-1], widths[1:], activations):
+        W = params[:, offset : offset + j * k].reshape(n, j, k)
+        offset += j * k
+        h = torch.einsum("bk,njk->nbj", x, W) if h is None else torch.einsum("nbk,njk->nbj", h, W)
+        if has_bias:
+            h = h + params[:, None, offset : offset + j]
+            offset += j
+        name = POPULATION_FORWARD_ACTIVATIONS[act]
+        if name != "identity":
+            h = getattr(torch, name)(h)
+    return h
 
 
 # ============================================================================

@@ -28,6 +28,9 @@ void adam_step_graphsafe(torch::Tensor step_out, torch::Tensor grad, torch::Tens
                          torch::Tensor t_buf, double stepsize, double beta1, double beta2, double epsilon);
 torch::Tensor population_mlp_forward(torch::Tensor params, torch::Tensor obs, std::vector<int64_t> widths,
                                      std::vector<int64_t> activations, bool has_bias);
+torch::Tensor population_mlp_forward_shared(torch::Tensor params, torch::Tensor x, std::vector<int64_t> widths,
+                                            std::vector<int64_t> activations, bool has_bias);
+int64_t population_mlp_forward_shared_batch_tile(std::vector<int64_t> widths);
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
@@ -85,6 +88,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "K13: forward of a dense policy stack (1-4 Linear layers; activation codes 0 identity, 1 tanh, 2 ReLU) for "
           "every member's own flat parameter vector; fp32, returns [n, widths[-1]]",
           py::arg("params"), py::arg("obs"), py::arg("widths"), py::arg("activations"), py::arg("has_bias"));
+    m.def("population_mlp_forward_shared", &ea::population_mlp_forward_shared,
+          "K14: forward of a dense stack (as K13 describes it) for every member's own flat parameter vector on ONE "
+          "shared minibatch x [B, widths[0]], on fp32 MFMA; fp32, returns [n, B, widths[-1]]",
+          py::arg("params"), py::arg("x"), py::arg("widths"), py::arg("activations"), py::arg("has_bias"));
+    m.def("population_mlp_forward_shared_batch_tile", &ea::population_mlp_forward_shared_batch_tile,
+          "K14: rows per batch tile (16, 32 or 64) the kernel takes for these widths (host only)", py::arg("widths"));
     // Both rollout entry points take `obs_stats_out` either as one tensor, to
     // which the summed statistics are ADDED and a fresh fitness tensor is
     // returned, or as a pair (obs_stats_out, fitness_out) of plain outputs:

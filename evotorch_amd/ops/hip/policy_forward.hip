@@ -10,8 +10,9 @@
 //
 // The work is a GEMV chain per member: every weight is read exactly once and
 // no operand is shared between members, so there is nothing for a matrix
-// instruction to reuse (and CDNA4 has no fp32-input MFMA). The kernel is
-// bound by weight bandwidth and by the latency of the layer chain.
+// instruction to reuse. The kernel is bound by weight bandwidth and by the
+// latency of the layer chain. (The shared-minibatch forward, where members
+// do share an operand, is K14, policy_forward_shared.hip.)
 //
 // Work split
 //   * A member is owned by ONE wave; a 256-thread block carries
@@ -47,15 +48,13 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include "check.h"
+#include "policy_common.h"
 #include "reduce.h"
 #include "rollout_common.h"
 
 namespace ea {
 
-constexpr int kMaxLayers = 4;
-constexpr int kMaxWidth = 1024;
 constexpr int kMembersPerBlock = 4;  // one wave each
-enum PolicyActivation : int { kActIdentity = 0, kActTanh = 1, kActRelu = 2 };
 
 // The stack description travels by value in the kernel arguments.
 struct PolicyForwardArgs {
@@ -70,8 +69,6 @@ struct PolicyForwardArgs {
     int act[kMaxLayers];
     int group[kMaxLayers];  // lanes per row group: 8, 16 or 64
 };
-
-typedef float floatx4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
 // Sum over each group of G lanes, valid in the group's LAST lane.
 template <int G>
@@ -93,12 +90,6 @@ __device__ __forceinline__ float group_sum(float x) {
         }
         return x;
     }
-}
-
-__device__ __forceinline__ float policy_activation(float v, int act) {
-    if (act == kActTanh) return tanhf(v);             // the accurate one, not tanh_fast
-    if (act == kActRelu) return v < 0.0f ? 0.0f : v;  // NaN passes, as torch.relu passes it
-    return v;
 }
 
 // Orders this wave's LDS stores before its later LDS loads (other lanes' data).
@@ -208,25 +199,10 @@ torch::Tensor population_mlp_forward(torch::Tensor params, torch::Tensor obs, st
                                      std::vector<int64_t> activations, bool has_bias) {
     check_primary(params, "params", 2);
     TORCH_CHECK(params.scalar_type() == torch::kFloat32, "params must be float32, got ", params.scalar_type());
-    const int64_t layers = (int64_t)widths.size() - 1;
-    TORCH_CHECK(layers >= 1 && layers <= kMaxLayers, "widths must describe 1 to ", kMaxLayers,
-                " Linear layers (2 to ", kMaxLayers + 1, " entries), got ", widths.size(), " entries");
-    TORCH_CHECK((int64_t)activations.size() == layers, "activations must have one code per layer (", layers,
-                "), got ", activations.size());
     PolicyForwardArgs args{};
-    int64_t expected = 0;
-    for (int64_t i = 0; i <= layers; ++i) {
-        TORCH_CHECK(widths[i] >= 1 && widths[i] <= kMaxWidth, "widths[", i, "] must be in [1, ", kMaxWidth, "], got ",
-                    widths[i]);
-        args.width[i] = (int)widths[i];
-    }
-    for (int64_t i = 0; i < layers; ++i) {
-        TORCH_CHECK(activations[i] >= kActIdentity && activations[i] <= kActRelu, "activations[", i,
-                    "] must be 0 (identity), 1 (tanh) or 2 (ReLU), got ", activations[i]);
-        args.act[i] = (int)activations[i];
-        args.group[i] = policy_group_width(args.width[i]);
-        expected += widths[i + 1] * widths[i] + (has_bias ? widths[i + 1] : 0);
-    }
+    const int64_t expected = check_dense_stack(widths, activations, has_bias, args.width, args.act);
+    const int64_t layers = (int64_t)widths.size() - 1;
+    for (int64_t i = 0; i < layers; ++i) args.group[i] = policy_group_width(args.width[i]);
     const int64_t n = params.size(0), L = params.size(1);
     TORCH_CHECK(L == expected, "params must hold ", expected, " values per member for this stack, got L = ", L);
     TORCH_CHECK(n <= INT_MAX / kMaxWidth, "params: too many members (", n, ")");
