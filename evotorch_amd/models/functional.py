@@ -11,7 +11,9 @@ as ONE kernel launch, `ops.population_forward` (K13,
 ops/hip/policy_forward.hip), and the same stack applied by every member to
 one shared minibatch (`forward_shared`, SupervisedNE's evaluation) is a
 GEMM chain per member on fp32 MFMA, `ops.population_forward_shared` (K14,
-ops/hip/policy_forward_shared.hip). Every other module goes through
+ops/hip/policy_forward_shared.hip), or on request on bf16 MFMA,
+`ops.population_forward_shared_bf16` (K15,
+ops/hip/policy_forward_shared_bf16.hip). Every other module goes through
 `torch.func.vmap` over `functional_call`, which lowers population-batched
 layers to library calls. The whole-episode fused path for the synthetic
 environment lives in evotorch_amd/ops/hip/rollout.hip.
@@ -125,13 +127,16 @@ class ModuleExpectingFlatParameters:
             return False  # the kernel has no backward
         return ops.hip_for(flat_params) is not None
 
-    def takes_shared_kernel(self, flat_params: torch.Tensor, x) -> bool:
-        """Whether `forward_shared(flat_params, x)` is
-        `ops.population_forward_shared`'s: a dense stack, 2-D fp32 ROCm
-        parameters, `x` 2-D fp32 of width D0 on the same device, no
-        gradient asked for, the HIP path switched on, and widths narrow
-        enough for the kernel's 32-row batch tiles (wider stacks measured
-        slower than the vmap path)."""
+    def takes_shared_kernel(self, flat_params: torch.Tensor, x, precision: str = "fp32") -> bool:
+        """Whether `forward_shared(flat_params, x, precision)` is one kernel
+        launch: a dense stack, 2-D fp32 ROCm parameters, `x` 2-D fp32 of
+        width D0 on the same device, no gradient asked for, the HIP path
+        switched on, and, for "fp32" (`ops.population_forward_shared`),
+        widths narrow enough for that kernel's 32-row batch tiles (wider
+        stacks measured slower than the vmap path). "bf16"
+        (`ops.population_forward_shared_bf16`) takes stacks of any width."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f'precision must be "fp32" or "bf16", got {precision!r}')
         if self._dense_stack is None or not isinstance(x, torch.Tensor):
             return False
         if flat_params.device.type != "cuda" or flat_params.dtype != torch.float32:
@@ -143,19 +148,28 @@ class ModuleExpectingFlatParameters:
         if x.ndim != 2 or x.shape[1] != self._dense_stack[0][0]:
             return False
         if torch.is_grad_enabled() and (flat_params.requires_grad or x.requires_grad):
-            return False  # the kernel has no backward
+            return False  # the kernels have no backward
         mod = ops.hip_for(flat_params)
         if mod is None:
             return False
+        if precision == "bf16":
+            return True
         if self._shared_tile is None:
             self._shared_tile = mod.population_mlp_forward_shared_batch_tile(self._dense_stack[0])
         return self._shared_tile >= ops.POPULATION_FORWARD_SHARED_MIN_TILE
 
-    def forward_shared(self, flat_params: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    def forward_shared(self, flat_params: torch.Tensor, x: torch.Tensor, precision: str = "fp32") -> torch.Tensor:
         """Every member of the 2-D `flat_params` (n, L) applied to the same
         input batch `x`: (n, B, *out). One `ops.population_forward_shared`
-        launch where `takes_shared_kernel` holds, else vmapped."""
-        if self.takes_shared_kernel(flat_params, x):
+        launch where `takes_shared_kernel` holds, else vmapped.
+
+        `precision="bf16"` asks for `ops.population_forward_shared_bf16`
+        instead: weights, `x` and hidden activations rounded to bfloat16,
+        sums, bias and activations in fp32. Where `takes_shared_kernel`
+        does not hold for it, the call is the vmapped fp32 one."""
+        if self.takes_shared_kernel(flat_params, x, precision):
+            if precision == "bf16":
+                return ops.population_forward_shared_bf16(flat_params, x, *self._dense_stack)
             return ops.population_forward_shared(flat_params, x, *self._dense_stack)
         return torch.func.vmap(self._single, in_dims=(0, None))(flat_params, x)
 

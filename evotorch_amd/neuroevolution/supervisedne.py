@@ -9,8 +9,9 @@ MI355X-native evaluation path: instead of looping solutions through one
 network, the whole population is evaluated on the minibatch in a single
 batched forward when `vectorized_eval=True` (default for
 common_minibatch mode): one fp32-MFMA kernel launch for a dense stack on
-a 2-D fp32 ROCm minibatch (`forward_shared`, K14), vmapped (rocBLAS
-batched GEMMs) otherwise.
+a 2-D fp32 ROCm minibatch (`forward_shared`, K14; with
+`forward_precision="bf16"` one bf16-MFMA launch, K15, for stacks of any
+width), vmapped (rocBLAS batched GEMMs) otherwise.
 """
 
 from typing import Callable, Optional, Union
@@ -28,6 +29,18 @@ __all__ = ["SupervisedNE"]
 
 
 class SupervisedNE(NEProblem):
+    """Neuroevolution of a network on a dataset and a loss.
+
+    `forward_precision` ("fp32" by default) is the precision of the
+    whole-population forward of a dense stack on a 2-D fp32 ROCm minibatch.
+    "bf16" rounds weights, minibatch and hidden activations to bfloat16 and
+    keeps sums, biases and activations in fp32
+    (`ops.population_forward_shared_bf16`): one kernel launch for stacks of
+    any width up to 1024, wide ones such as 784 -> 128 -> 10 included, at
+    a rounding error far below the minibatch noise of the fitness. Nets
+    that are not a dense stack, or that bring their own
+    `population_forward`, are evaluated as with "fp32"."""
+
     def __init__(
         self,
         dataset: Dataset,
@@ -43,12 +56,15 @@ class SupervisedNE(NEProblem):
         device=None,
         seed: Optional[int] = None,
         vectorized_eval: bool = True,
+        forward_precision: str = "fp32",
         subbatch_size: Optional[int] = None,
         num_subbatches: Optional[int] = None,
         num_actors=None,
         num_gpus_per_actor=None,
         actor_config=None,
     ):
+        if forward_precision not in ("fp32", "bf16"):
+            raise ValueError(f'forward_precision must be "fp32" or "bf16", got {forward_precision!r}')
         # num_subbatches/subbatch_size keep their SupervisedNE meaning
         # (solutions per common minibatch) and are consumed here, not by
         # the evaluation pool.
@@ -69,6 +85,7 @@ class SupervisedNE(NEProblem):
         self._num_minibatches = max(1, int(num_minibatches)) if num_minibatches is not None else 1
         self._common_minibatch = bool(common_minibatch)
         self._vectorized_eval = bool(vectorized_eval)
+        self._forward_precision = forward_precision
         self._dataloader: Optional[DataLoader] = None
         self._dataloader_iter = None
         self._fmodule = None
@@ -166,9 +183,10 @@ class SupervisedNE(NEProblem):
                     if pop_fwd is not None:
                         preds = pop_fwd(params[start:stop], x)
                         chunk = torch.func.vmap(lambda p: self._loss(p, y))(preds)
-                    elif self._fmodule.takes_shared_kernel(params[start:stop], x):
-                        # dense stack on a 2-D fp32 ROCm minibatch: one K14 launch
-                        preds = ops.population_forward_shared(params[start:stop], x, *self._fmodule._dense_stack)
+                    elif self._fmodule.takes_shared_kernel(params[start:stop], x, self._forward_precision):
+                        # dense stack on a 2-D fp32 ROCm minibatch: one K14 launch, or one K15 launch for "bf16"
+                        forward = ops.population_forward_shared_bf16 if self._forward_precision == "bf16" else ops.population_forward_shared
+                        preds = forward(params[start:stop], x, *self._fmodule._dense_stack)
                         chunk = torch.func.vmap(lambda p: self._loss(p, y))(preds)
                     else:
                         def member_loss(flat):

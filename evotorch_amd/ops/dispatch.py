@@ -15,8 +15,9 @@ snes_gradients, K4 clipup_step / adam_step, K4b gaussian_clipup_update, K12
 obsnorm_pack / obsnorm_merge, K5 cma_update_c, K5b potrf_tile,
 K7 pareto_ranks / domination_counts, K9 mapelites_assign (routed from
 algorithms/mapelites.py), K10+K11 rollout_linear (called from
-neuroevolution/synthetic.py), K13 population_forward and K14
-population_forward_shared (routed from models/functional.py).
+neuroevolution/synthetic.py), K13 population_forward, K14
+population_forward_shared and K15 population_forward_shared_bf16 (routed
+from models/functional.py).
 
 The launchers check every operand (ops/hip/check.h): dense, on the primary
 tensor's device, of its dtype and of exactly the length the kernel reads.
@@ -55,6 +56,7 @@ __all__ = [
     "cma_update_c_",
     "population_forward",
     "population_forward_shared",
+    "population_forward_shared_bf16",
     "POPULATION_FORWARD_MAX_LAYERS",
     "POPULATION_FORWARD_MAX_WIDTH",
     "POPULATION_FORWARD_ACTIVATIONS",
@@ -616,6 +618,52 @@ def population_forward_shared(params: torch.Tensor, x: torch.Tensor, widths, act
         W = params[:, offset : offset + j * k].reshape(n, j, k)
         offset += j * k
         h = torch.einsum("bk,njk->nbj", x, W) if h is None else torch.einsum("nbk,njk->nbj", h, W)
+        if has_bias:
+            h = h + params[:, None, offset : offset + j]
+            offset += j
+        name = POPULATION_FORWARD_ACTIVATIONS[act]
+        if name != "identity":
+            h = getattr(torch, name)(h)
+    return h
+
+
+# ============================================================================
+# K15 — the same forward with bf16 operands (opt-in)
+# ============================================================================
+
+
+def population_forward_shared_bf16(params: torch.Tensor, x: torch.Tensor, widths, activations, has_bias: bool) -> torch.Tensor:
+    """`population_forward_shared` with every layer's weight matrix and
+    input rounded to bfloat16 (nearest even): `x` for the first layer, the
+    previous layer's activated output after that. Products are summed, the
+    bias added and the activation applied in the tensors' own dtype, and the
+    last layer's result is not rounded. Arguments, layout and result shape
+    are `population_forward_shared`'s; inputs and output are fp32.
+
+    fp32 ROCm tensors take ONE kernel launch on bf16 MFMA with fp32 sums
+    (ops/hip/policy_forward_shared_bf16.hip), hipGraph-capturable, and
+    `out[m, b]` depends bit for bit on `params[m]`, `x[b]` and the stack
+    description only. CPU tensors, other dtypes, and ROCm tensors under
+    `eager_on_gpu()` run the eager chain below; in float64 it is the
+    kernel's oracle."""
+    widths, activations = _stack_description(widths, activations)
+    if params.ndim != 2 or x.ndim != 2 or x.shape[1] != widths[0]:
+        raise ValueError(f"expected params (n, L) and x (B, {widths[0]}), got {tuple(params.shape)} and {tuple(x.shape)}")
+    mod = hip_for(params) if params.dtype == torch.float32 else None
+    if mod is not None:
+        return mod.population_mlp_forward_shared_bf16(params.contiguous(), *_dense(params, x), widths, activations, bool(has_bias))
+    expected = sum(j * k + (j if has_bias else 0) for k, j in zip(widths[:-1], widths[1:]))
+    if params.shape[1] != expected:
+        raise ValueError(f"this stack takes {expected} parameters per member, got {params.shape[1]}")
+
+    def rounded(t):
+        return t.bfloat16().to(t.dtype)
+
+    n, offset, h = params.shape[0], 0, None
+    for k, j, act in zip(widths[:-1], widths[1:], activations):
+        W = rounded(params[:, offset : offset + j * k]).reshape(n, j, k)
+        offset += j * k
+        h = torch.einsum("bk,njk->nbj", rounded(x), W) if h is None else torch.einsum("nbk,njk->nbj", rounded(h), W)
         if has_bias:
             h = h + params[:, None, offset : offset + j]
             offset += j

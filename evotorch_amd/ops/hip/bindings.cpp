@@ -31,6 +31,10 @@ torch::Tensor population_mlp_forward(torch::Tensor params, torch::Tensor obs, st
 torch::Tensor population_mlp_forward_shared(torch::Tensor params, torch::Tensor x, std::vector<int64_t> widths,
                                             std::vector<int64_t> activations, bool has_bias);
 int64_t population_mlp_forward_shared_batch_tile(std::vector<int64_t> widths);
+torch::Tensor population_mlp_forward_shared_bf16(torch::Tensor params, torch::Tensor x, std::vector<int64_t> widths,
+                                                 std::vector<int64_t> activations, bool has_bias,
+                                                 int64_t batch_tile);
+int64_t population_mlp_forward_shared_bf16_batch_tile(std::vector<int64_t> widths);
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
@@ -94,6 +98,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("params"), py::arg("x"), py::arg("widths"), py::arg("activations"), py::arg("has_bias"));
     m.def("population_mlp_forward_shared_batch_tile", &ea::population_mlp_forward_shared_batch_tile,
           "K14: rows per batch tile (16, 32 or 64) the kernel takes for these widths (host only)", py::arg("widths"));
+    m.def("population_mlp_forward_shared_bf16", &ea::population_mlp_forward_shared_bf16,
+          "K15: K14's forward with weights, x and hidden activations rounded to bf16, on bf16 MFMA with fp32 sums, "
+          "bias and activation; fp32 in and out, returns [n, B, widths[-1]]. batch_tile 0 takes the kernel's own "
+          "rule, 32 or 64 overrides it (for measuring)",
+          py::arg("params"), py::arg("x"), py::arg("widths"), py::arg("activations"), py::arg("has_bias"),
+          py::arg("batch_tile") = 0);
+    m.def("population_mlp_forward_shared_bf16_batch_tile", &ea::population_mlp_forward_shared_bf16_batch_tile,
+          "K15: rows per batch tile (32 or 64) the kernel takes for these widths (host only)", py::arg("widths"));
     // Both rollout entry points take `obs_stats_out` either as one tensor, to
     // which the summed statistics are ADDED and a fresh fitness tensor is
     // returned, or as a pair (obs_stats_out, fitness_out) of plain outputs:

@@ -1,12 +1,15 @@
-// What the two population-batched dense-stack forwards share: K13
-// (policy_forward.hip, every member on its own observation) and K14
-// (policy_forward_shared.hip, every member on one shared minibatch).
+// What the population-batched dense-stack forwards share: K13
+// (policy_forward.hip, every member on its own observation), K14
+// (policy_forward_shared.hip, every member on one shared minibatch, fp32
+// MFMA) and K15 (policy_forward_shared_bf16.hip, the same on bf16 MFMA).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <c10/util/Exception.h>
 
 #include <cstdint>
 #include <vector>
+
+#include "rollout_common.h"
 
 namespace ea {
 
@@ -20,6 +23,34 @@ __device__ __forceinline__ float policy_activation(float v, int act) {
     if (act == kActTanh) return tanhf(v);             // the accurate one, not tanh_fast
     if (act == kActRelu) return v < 0.0f ? 0.0f : v;  // NaN passes, as torch.relu passes it
     return v;
+}
+
+// K14 and K15: what a shared-minibatch launch passes to its kernel.
+constexpr int kXcds = 8;  // the hardware deals consecutive blocks to the XCDs in turn
+
+struct SharedForwardArgs {
+    const float* params;  // [n][L]
+    const float* x;       // [B][width[0]]
+    float* out;           // [n][B][width[layers]]
+    int B;
+    int tiles;   // batch tiles per member
+    int blocks;  // n * tiles logical blocks
+    long L;
+    int layers;
+    int has_bias;
+    int width[kMaxLayers + 1];
+    int act[kMaxLayers];
+};
+
+// The 16-byte word W[row][k0 .. k0+3] with everything past K zero; reads
+// nothing outside the row.
+__device__ __forceinline__ floatx4 shared_weight_word(const float* __restrict__ Wr, int K, int k0) {
+    if (k0 + 4 <= K) return *reinterpret_cast<const floatx4_a4*>(Wr + k0);
+    floatx4 w = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (k0 < K) w.x = Wr[k0];
+    if (k0 + 1 < K) w.y = Wr[k0 + 1];
+    if (k0 + 2 < K) w.z = Wr[k0 + 2];
+    return w;
 }
 
 // Checks a stack description (1 to kMaxLayers Linear layers, widths in

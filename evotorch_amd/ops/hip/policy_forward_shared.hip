@@ -68,23 +68,8 @@ namespace ea {
 constexpr int kSharedThreads = 256;
 constexpr int kSharedWaves = kSharedThreads / 64;
 constexpr int kPrefetch = 4;  // weight words in flight per lane, in super-steps
-constexpr int kXcds = 8;      // the hardware deals consecutive blocks to the XCDs in turn
 // two blocks share a CU's 160 KB of LDS while each stays within this
 constexpr size_t kSharedLdsPerBlock = 80 * 1024;
-
-struct SharedForwardArgs {
-    const float* params;  // [n][L]
-    const float* x;       // [B][width[0]]
-    float* out;           // [n][B][width[layers]]
-    int B;
-    int tiles;   // batch tiles per member
-    int blocks;  // n * tiles logical blocks
-    long L;
-    int layers;
-    int has_bias;
-    int width[kMaxLayers + 1];
-    int act[kMaxLayers];
-};
 
 // The LDS layout, stated once for the kernel's carve-up and the launcher's
 // footprint: buffer 0 [bt][shared_stride(.., 0)] floats, then buffer 1
@@ -100,17 +85,6 @@ __host__ __device__ inline int shared_stride(const int* width, int layers, int p
 
 __host__ __device__ inline size_t shared_lds_bytes(const int* width, int layers, int bt) {
     return (size_t)bt * (shared_stride(width, layers, 0) + shared_stride(width, layers, 1)) * sizeof(float);
-}
-
-// The 16-byte word W[row][k0 .. k0+3] with everything past K zero; reads
-// nothing outside the row.
-__device__ __forceinline__ floatx4 shared_weight_word(const float* __restrict__ Wr, int K, int k0) {
-    if (k0 + 4 <= K) return *reinterpret_cast<const floatx4_a4*>(Wr + k0);
-    floatx4 w = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (k0 < K) w.x = Wr[k0];
-    if (k0 + 1 < K) w.y = Wr[k0 + 1];
-    if (k0 + 2 < K) w.z = Wr[k0 + 2];
-    return w;
 }
 
 template <int BT>

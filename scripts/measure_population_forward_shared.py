@@ -14,6 +14,12 @@ held on the vmap path.
     python scripts/measure_population_forward_shared.py [--popsize 1024] [--batch 128] [--rounds 10]
 
 Prints one JSON line per stack and one for the generation. Run it twice.
+
+With --precision bf16, (a) times K15 (`ops.population_forward_shared_bf16`)
+beside K14 called directly and the fp32 vmap path, and K15 with its batch
+tile forced to 32 and to 64 rows where the stack's LDS rows allow it (the
+measurement behind its tile rule); (b) is left out. `max_abs_diff` is then
+K15 against the vmap path: bf16 rounding, not an error of the kernel.
 """
 
 import argparse
@@ -36,6 +42,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=20, help="forwards per timed sample in (a)")
+    ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm GPU"
 
@@ -63,13 +70,25 @@ def main():
 
         # the op itself: forward_shared routes only the stacks on which the kernel won here
         variants = {"kernel": lambda: ops.population_forward_shared(params, x, *fmodule._dense_stack), "vmap": vmapped}
+        if args.precision == "bf16":
+            mod = ops.hip_required()
+            variants = {"kernel": lambda: ops.population_forward_shared_bf16(params, x, *fmodule._dense_stack),
+                        "k14": variants["kernel"], "vmap": vmapped}
+            for bt in (32, 64):
+                try:
+                    mod.population_mlp_forward_shared_bf16(params, x, *fmodule._dense_stack, bt)
+                except RuntimeError:  # this tile does not fit the LDS at these widths
+                    continue
+                variants[f"kernel_bt{bt}"] = lambda bt=bt: mod.population_mlp_forward_shared_bf16(params, x, *fmodule._dense_stack, bt)
         max_diff = (variants["kernel"]() - variants["vmap"]()).abs().max().item()
         rows = _alternate(variants, args.rounds, args.warmup, args.reps)
-        print(json.dumps({"forward": name, "n": n, "B": B, "rounds": args.rounds, "reps": args.reps,
-                          "max_abs_diff": max_diff,
+        print(json.dumps({"forward": name, "precision": args.precision, "n": n, "B": B, "rounds": args.rounds,
+                          "reps": args.reps, "max_abs_diff": max_diff,
                           "vmap_over_kernel": rows["vmap"]["mean_ms"] / rows["kernel"]["mean_ms"], "variants": rows}),
               flush=True)
 
+    if args.precision == "bf16":
+        return
     X, Y = torch.randn(64 * B, 8, generator=g), torch.randn(64 * B, 1, generator=g)
     generations = {}
     for kernel in (True, False):

@@ -27,6 +27,7 @@ setup(
                 os.path.join(SRC, "obsnorm.hip"),
                 os.path.join(SRC, "policy_forward.hip"),
                 os.path.join(SRC, "policy_forward_shared.hip"),
+                os.path.join(SRC, "policy_forward_shared_bf16.hip"),
                 os.path.join(SRC, "rollout.hip"),
                 os.path.join(SRC, "rollout_v7.hip"),
                 os.path.join(SRC, "rollout_m7.hip"),
