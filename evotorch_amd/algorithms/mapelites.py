@@ -103,7 +103,13 @@ class MAPElites(SearchAlgorithm, SinglePopulationAlgorithmMixin, ExtendedPopulat
         f = features.unsqueeze(0)  # (1, N, F)
         inside = ((f >= lo) & (f <= hi)).all(dim=-1)  # (C, N)
         masked = torch.where(inside, utils.unsqueeze(0), torch.full_like(utils, float("-inf")).unsqueeze(0).expand_as(inside))
-        best_idx = masked.argmax(dim=1)  # (C,)
+        # The first INSIDE row that attains the cell's best utility, as the
+        # kernel picks it. An argmax over `masked` alone cannot tell an
+        # inside row of utility -inf (a NaN fitness) from an outside row: in
+        # a cell whose inside rows are all -inf it would return row 0.
+        cell_best = masked.max(dim=1, keepdim=True).values  # (C, 1)
+        attains = inside & (utils.unsqueeze(0) == cell_best)
+        best_idx = attains.to(torch.uint8).argmax(dim=1)  # (C,); 0 for an empty cell
         any_valid = inside.any(dim=1)
         return best_idx, any_valid
 

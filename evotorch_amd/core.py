@@ -85,7 +85,9 @@ def _compute_pareto_ranks(utils: torch.Tensor, crowdsort: bool = True, min_assig
     eager masked reductions on CPU. `min_assigned` allows the peel to
     stop early once that many solutions hold final ranks (exact for
     take_best(n): the boundary front is always fully peeled, so the
-    first n of the (rank, crowding) order are unchanged)."""
+    first n of the (rank, crowding) order are unchanged). Both paths
+    compare float64 utilities as float64, so they rank the same rows
+    apart."""
     if utils.device.type == "cuda":
         from . import ops
 

@@ -680,7 +680,14 @@ def population_forward_shared_bf16(params: torch.Tensor, x: torch.Tensor, widths
 
 def domination_counts(utils: torch.Tensor) -> torch.Tensor:
     """Per solution: how many others dominate it. `utils` is (N, M) with
-    higher-is-better columns."""
+    higher-is-better columns.
+
+    A row dominates another when it is `>=` in every column and `>` in at
+    least one, so equal rows do not dominate each other and a row holding a
+    NaN neither dominates nor is dominated. The comparison runs in the
+    input's precision: fp64 utilities are compared as fp64 on both devices,
+    every other dtype is compared as fp32 on the GPU (exact for fp16 and
+    bf16). An empty input gives an empty result."""
     mod = hip_for(utils)
     if mod is not None:
         return mod.domination_counts(utils).to(torch.int64)
@@ -695,7 +702,12 @@ def pareto_ranks(utils: torch.Tensor, min_assigned: Optional[int] = None) -> tor
     by count + front peeling without the N x N matrix. With
     `min_assigned`, peeling stops once that many solutions hold final
     ranks (take_best(n) only needs the fronts crossing n); the rest get a
-    shared beyond-last rank."""
+    shared beyond-last rank, one past the last front peeled.
+
+    Domination, ties, NaN rows and precision follow `domination_counts`:
+    equal rows share a front, and fp64 utilities that differ below fp32
+    resolution are ranked apart, as on the CPU. The result does not depend
+    on the order in which the kernel's atomics fill a front."""
     mod = hip_for(utils)
     if mod is not None:
         return mod.pareto_ranks(utils, int(min_assigned or 0))

@@ -3,8 +3,14 @@
 // matrix (the eager path's (N, N, M) broadcast explodes past ~10k
 // solutions; these kernels are O(N²·M) compute but O(N) memory).
 //
-// utils is (N, M) fp32 with HIGHER IS BETTER for every column (senses
-// already folded by the caller). Each thread owns one solution j, caches
+// utils is (N, M) with HIGHER IS BETTER for every column (senses already
+// folded by the caller). The kernels compare in the input's precision:
+// they are instantiated for float and double, fp64 input is compared as
+// fp64 (two rows that differ below fp32 resolution do not tie), and every
+// other dtype is upcast to float (exact for fp16/bf16). Ties follow the
+// definition: a row dominates another when it is >= everywhere and >
+// somewhere, so equal rows do not dominate each other and share a front.
+// Each thread owns one solution j, caches
 // its own objective row in registers, and streams the other rows — row i
 // is read by all threads of a wave simultaneously (broadcast, L2-cached).
 //
@@ -24,10 +30,11 @@ namespace ea {
 constexpr int kMaxObjCache = 16;
 
 // a dominates b: no worse in every objective, strictly better in one
-__device__ __forceinline__ bool dominates_rows(const float* __restrict__ a, const float* __restrict__ b, int m) {
+template <typename T>
+__device__ __forceinline__ bool dominates_rows(const T* __restrict__ a, const T* __restrict__ b, int m) {
     bool ge_all = true, gt_any = false;
     for (int k = 0; k < m; ++k) {
-        const float o = a[k];
+        const T o = a[k];
         ge_all &= (o >= b[k]);
         gt_any |= (o > b[k]);
     }
@@ -38,15 +45,17 @@ __device__ __forceinline__ bool dominates_rows(const float* __restrict__ a, cons
 // register array `mine` when it fits (`cached`), else re-read from `own`
 // in global memory. Two calls on purpose: selecting one pointer between
 // the two (`me = cached ? mine : own`) sends the array to scratch.
-__device__ __forceinline__ bool dominated_by(const float* __restrict__ other, const float (&mine)[kMaxObjCache],
-                                             bool cached, const float* __restrict__ own, int m) {
+template <typename T>
+__device__ __forceinline__ bool dominated_by(const T* __restrict__ other, const T (&mine)[kMaxObjCache], bool cached,
+                                             const T* __restrict__ own, int m) {
     return cached ? dominates_rows(other, mine, m) : dominates_rows(other, own, m);
 }
 
-__global__ void domination_counts_kernel(const float* __restrict__ utils, int* __restrict__ counts, int64_t n, int m) {
+template <typename T>
+__global__ void domination_counts_kernel(const T* __restrict__ utils, int* __restrict__ counts, int64_t n, int m) {
     const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (j >= n) return;
-    float mine[kMaxObjCache];
+    T mine[kMaxObjCache];
     const bool cached = m <= kMaxObjCache;
     if (cached) {
         for (int k = 0; k < m; ++k) mine[k] = utils[j * m + k];
@@ -83,13 +92,14 @@ __global__ void zero_counts_kernel(int* __restrict__ front_counts, int batch) {
     if (j < batch) front_counts[j] = 0;
 }
 
-__global__ void subtract_front_kernel(const float* __restrict__ utils, int* __restrict__ counts,
+template <typename T>
+__global__ void subtract_front_kernel(const T* __restrict__ utils, int* __restrict__ counts,
                                       const int* __restrict__ front_list, const int* __restrict__ front_count,
                                       int64_t n, int m) {
     const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (j >= n) return;
     if (counts[j] < 0) return;  // already assigned
-    float mine[kMaxObjCache];
+    T mine[kMaxObjCache];
     const bool cached = m <= kMaxObjCache;
     if (cached) {
         for (int k = 0; k < m; ++k) mine[k] = utils[j * m + k];
@@ -101,17 +111,32 @@ __global__ void subtract_front_kernel(const float* __restrict__ utils, int* __re
     counts[j] -= removed;
 }
 
+// The dense operand the kernels compare: fp64 stays fp64, every other dtype
+// becomes fp32.
+static torch::Tensor compare_operand(const torch::Tensor& t, bool as_double) {
+    return t.to(as_double ? torch::kFloat64 : torch::kFloat32).contiguous();
+}
+
+template <typename T>
+static void launch_domination_counts(const torch::Tensor& utils_c, torch::Tensor& counts) {
+    const int64_t n = utils_c.size(0);
+    const int threads = 256;
+    hipLaunchKernelGGL(domination_counts_kernel<T>, dim3(grid_for(n, threads)), dim3(threads), 0,
+                       at::cuda::getCurrentCUDAStream(), utils_c.data_ptr<T>(), counts.data_ptr<int>(), n,
+                       (int)utils_c.size(1));
+}
+
 torch::Tensor domination_counts(torch::Tensor utils) {
     TORCH_CHECK(utils.is_cuda() && utils.dim() == 2, "utils must be a 2-D ROCm tensor");
-    auto utils_f = utils.to(torch::kFloat32).contiguous();
-    const int64_t n = utils_f.size(0);
-    const int m = (int)utils_f.size(1);
-    auto counts = torch::empty({n}, utils_f.options().dtype(torch::kInt32));
-    const int threads = 256;
-    const int blocks = grid_for(n, threads);
-    auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(domination_counts_kernel, dim3(blocks), dim3(threads), 0, stream, utils_f.data_ptr<float>(),
-                       counts.data_ptr<int>(), n, m);
+    const bool as_double = utils.scalar_type() == torch::kFloat64;
+    auto utils_c = compare_operand(utils, as_double);
+    const int64_t n = utils_c.size(0);
+    auto counts = torch::empty({n}, utils_c.options().dtype(torch::kInt32));
+    if (n == 0) return counts;  // a grid of zero blocks is an invalid launch
+    if (as_double)
+        launch_domination_counts<double>(utils_c, counts);
+    else
+        launch_domination_counts<float>(utils_c, counts);
     return counts;
 }
 
@@ -120,9 +145,11 @@ torch::Tensor pareto_ranks(torch::Tensor utils, int64_t min_assigned) {
     // ranks (take_best(n) only needs the fronts crossing n); stragglers
     // get a beyond-last rank. 0 = full sort.
     TORCH_CHECK(utils.is_cuda() && utils.dim() == 2, "utils must be a 2-D ROCm tensor");
-    auto utils_f = utils.to(torch::kFloat32).contiguous();
+    const bool as_double = utils.scalar_type() == torch::kFloat64;
+    auto utils_f = compare_operand(utils, as_double);
     const int64_t n = utils_f.size(0);
     const int m = (int)utils_f.size(1);
+    if (n == 0) return torch::empty({0}, utils_f.options().dtype(torch::kInt64));  // nothing to launch
     if (min_assigned <= 0 || min_assigned > n) min_assigned = n;
     auto counts = domination_counts(utils_f);
     auto ranks = torch::full({n}, -1, utils_f.options().dtype(torch::kInt64));
@@ -148,8 +175,14 @@ torch::Tensor pareto_ranks(torch::Tensor utils, int64_t min_assigned) {
             hipLaunchKernelGGL(compact_front_kernel, dim3(blocks), dim3(threads), 0, stream, counts.data_ptr<int>(),
                                ranks.data_ptr<int64_t>(), front_list.data_ptr<int>(), slot, n,
                                front_index);
-            hipLaunchKernelGGL(subtract_front_kernel, dim3(blocks), dim3(threads), 0, stream, utils_f.data_ptr<float>(),
-                               counts.data_ptr<int>(), front_list.data_ptr<int>(), slot, n, m);
+            if (as_double)
+                hipLaunchKernelGGL(subtract_front_kernel<double>, dim3(blocks), dim3(threads), 0, stream,
+                                   utils_f.data_ptr<double>(), counts.data_ptr<int>(), front_list.data_ptr<int>(),
+                                   slot, n, m);
+            else
+                hipLaunchKernelGGL(subtract_front_kernel<float>, dim3(blocks), dim3(threads), 0, stream,
+                                   utils_f.data_ptr<float>(), counts.data_ptr<int>(), front_list.data_ptr<int>(),
+                                   slot, n, m);
             ++front_index;
         }
         const int64_t remaining = (counts >= 0).sum().item<int64_t>();  // one sync per batch
@@ -174,19 +207,26 @@ torch::Tensor pareto_ranks(torch::Tensor utils, int64_t min_assigned) {
 // C=10k × N=20k); this kernel streams the solutions once per cell thread
 // with O(C + N) memory. Feature rows are read wave-uniformly (broadcast,
 // L2-cached) like the domination kernels above.
+//
+// A row is inside a cell when lo <= x <= hi in every feature (a feature on
+// a shared edge is inside both cells, NaN is inside none); the cell keeps
+// the inside row of the largest utility, the FIRST one on ties, -inf
+// included. Boxes and features are compared in fp64 when either is fp64,
+// else in fp32; utilities are fp32 (the caller folds them to fp32).
 // ---------------------------------------------------------------------------
 
 constexpr int kMaxFeat = 16;
 
-__global__ void mapelites_assign_kernel(const float* __restrict__ grid,   // [C][F][2]
-                                        const float* __restrict__ feats,  // [N][F]
+template <typename T>
+__global__ void mapelites_assign_kernel(const T* __restrict__ grid,       // [C][F][2]
+                                        const T* __restrict__ feats,      // [N][F]
                                         const float* __restrict__ utils,  // [N] higher is better
                                         int64_t* __restrict__ best_idx,   // [C]
                                         bool* __restrict__ any_valid,     // [C]
                                         int64_t c_total, int64_t n, int f) {
     const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (c >= c_total) return;
-    float lo[kMaxFeat], hi[kMaxFeat];
+    T lo[kMaxFeat], hi[kMaxFeat];
     for (int k = 0; k < f; ++k) {
         lo[k] = grid[(c * f + k) * 2];
         hi[k] = grid[(c * f + k) * 2 + 1];
@@ -197,7 +237,7 @@ __global__ void mapelites_assign_kernel(const float* __restrict__ grid,   // [C]
     for (int64_t i = 0; i < n; ++i) {
         bool inside = true;
         for (int k = 0; k < f; ++k) {
-            const float x = feats[i * f + k];
+            const T x = feats[i * f + k];
             inside &= (x >= lo[k]) & (x <= hi[k]);
         }
         const float u = utils[i];
@@ -221,18 +261,25 @@ std::vector<torch::Tensor> mapelites_assign(torch::Tensor grid, torch::Tensor fe
     TORCH_CHECK(f <= kMaxFeat, "at most ", kMaxFeat, " feature dimensions");
     TORCH_CHECK(feats.size(1) == f, "feats must have ", f, " columns, got ", feats.size(1));
     TORCH_CHECK(utils.size(0) == feats.size(0), "utils must have ", feats.size(0), " entries, got ", utils.size(0));
-    auto grid_f = grid.to(torch::kFloat32).contiguous();
-    auto feats_f = feats.to(torch::kFloat32).contiguous();
+    const bool as_double = grid.scalar_type() == torch::kFloat64 || feats.scalar_type() == torch::kFloat64;
+    auto grid_f = compare_operand(grid, as_double);
+    auto feats_f = compare_operand(feats, as_double);
     auto utils_f = utils.to(torch::kFloat32).contiguous();
     const int64_t c_total = grid.size(0), n = feats.size(0);
     auto best = torch::zeros({c_total}, grid.options().dtype(torch::kInt64));
     auto valid = torch::zeros({c_total}, grid.options().dtype(torch::kBool));
+    if (c_total == 0) return {best, valid};  // a grid of zero blocks is an invalid launch
     const int threads = 256;
     const int blocks = grid_for(c_total, threads);
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(mapelites_assign_kernel, dim3(blocks), dim3(threads), 0, stream, grid_f.data_ptr<float>(),
-                       feats_f.data_ptr<float>(), utils_f.data_ptr<float>(), best.data_ptr<int64_t>(),
-                       valid.data_ptr<bool>(), c_total, n, f);
+    if (as_double)
+        hipLaunchKernelGGL(mapelites_assign_kernel<double>, dim3(blocks), dim3(threads), 0, stream,
+                           grid_f.data_ptr<double>(), feats_f.data_ptr<double>(), utils_f.data_ptr<float>(),
+                           best.data_ptr<int64_t>(), valid.data_ptr<bool>(), c_total, n, f);
+    else
+        hipLaunchKernelGGL(mapelites_assign_kernel<float>, dim3(blocks), dim3(threads), 0, stream,
+                           grid_f.data_ptr<float>(), feats_f.data_ptr<float>(), utils_f.data_ptr<float>(),
+                           best.data_ptr<int64_t>(), valid.data_ptr<bool>(), c_total, n, f);
     return {best, valid};
 }
 
