@@ -13,7 +13,11 @@ one shared minibatch (`forward_shared`, SupervisedNE's evaluation) is a
 GEMM chain per member on fp32 MFMA, `ops.population_forward_shared` (K14,
 ops/hip/policy_forward_shared.hip), or on request on bf16 MFMA,
 `ops.population_forward_shared_bf16` (K15,
-ops/hip/policy_forward_shared_bf16.hip). Every other module goes through
+ops/hip/policy_forward_shared_bf16.hip). A `MultiLayered` stack with one
+`RNN` or `LSTM` layer is recognised too (`recurrent_stack_description`);
+`models.Policy` runs its step as one launch,
+`ops.population_forward_recurrent` (K16,
+ops/hip/policy_forward_recurrent.hip), when asked to. Every other module goes through
 `torch.func.vmap` over `functional_call`, which lowers population-batched
 layers to library calls. The whole-episode fused path for the synthetic
 environment lives in evotorch_amd/ops/hip/rollout.hip.
@@ -26,9 +30,15 @@ import torch
 from torch import nn
 
 from .. import ops
+from .layers import LSTM, RNN
 from .multilayered import MultiLayered
 
-__all__ = ["ModuleExpectingFlatParameters", "dense_stack_description", "make_functional_module"]
+__all__ = [
+    "ModuleExpectingFlatParameters",
+    "dense_stack_description",
+    "make_functional_module",
+    "recurrent_stack_description",
+]
 
 
 def dense_stack_description(net: nn.Module) -> Optional[Tuple[list, list, bool]]:
@@ -74,6 +84,61 @@ def dense_stack_description(net: nn.Module) -> Optional[Tuple[list, list, bool]]
     return widths, activations, biases[0]
 
 
+def recurrent_stack_description(net: nn.Module) -> Optional[Tuple[list, list, list, bool, int]]:
+    """(kinds, widths, activation codes, has_bias, state_index) when `net`
+    is a recurrent stack that `ops.population_forward_recurrent` computes,
+    else None.
+
+    A recurrent stack is exactly a `MultiLayered` (what `>>` builds) whose
+    children are exactly `nn.Linear`, `nn.Tanh`, `nn.ReLU`, `layers.RNN` and
+    `layers.LSTM` instances (no subclasses), with exactly one recurrent
+    child; `state_index` is that child's position, its key in the state
+    dict. Otherwise the rules are `dense_stack_description`'s: 1 to 4
+    weighted layers that chain, widths up to 1024, the Linear layers all
+    with a bias or none, at most one activation after each Linear (none
+    after the recurrent layer, whose output is its state), no buffers, no
+    module used twice. `has_bias` is True for a stack without a Linear."""
+    if type(net) is not MultiLayered:
+        return None
+    layers = list(net)
+    if len(set(map(id, layers))) != len(layers) or next(net.buffers(), None) is not None:
+        return None
+    names = ops.POPULATION_FORWARD_ACTIVATIONS
+    codes = {nn.Tanh: names.index("tanh"), nn.ReLU: names.index("relu")}
+    kinds, widths, activations, biases, state_index = [], [], [], [], None
+    after_linear = False
+    for index, layer in enumerate(layers):
+        if type(layer) in codes:
+            if not after_linear:
+                return None
+            activations[-1] = codes[type(layer)]
+            after_linear = False
+            continue
+        if type(layer) is nn.Linear:
+            kind, k, j, act = "dense", layer.in_features, layer.out_features, "identity"
+            biases.append(layer.bias is not None)
+        elif type(layer) is RNN and state_index is None:
+            kind, k, j = "rnn", layer.input_size, layer.hidden_size
+            act = "tanh" if layer._act is torch.tanh else "relu"
+        elif type(layer) is LSTM and state_index is None:
+            kind, k, j, act = "lstm", layer.input_size, layer.hidden_size, "identity"
+        else:
+            return None
+        if widths and widths[-1] != k:
+            return None
+        if kind != "dense":
+            state_index = index
+        widths += [j] if widths else [k, j]
+        kinds.append(ops.POPULATION_FORWARD_KINDS.index(kind))
+        activations.append(names.index(act))
+        after_linear = kind == "dense"
+    if state_index is None or len(kinds) > ops.POPULATION_FORWARD_MAX_LAYERS or len(set(biases)) > 1:
+        return None
+    if not all(1 <= w <= ops.POPULATION_FORWARD_MAX_WIDTH for w in widths):
+        return None
+    return kinds, widths, activations, (biases[0] if biases else True), state_index
+
+
 class ModuleExpectingFlatParameters:
     """Wraps an nn.Module as a pure function `f(flat_params, *inputs)`.
 
@@ -89,6 +154,7 @@ class ModuleExpectingFlatParameters:
         self._length = sum(n for _, _, n in self._param_shapes)
         self._buffers = dict(self._net.named_buffers())
         self._dense_stack = dense_stack_description(self._net)
+        self._recurrent_stack = recurrent_stack_description(self._net)  # K16's, taken by models.Policy on request
         self._shared_tile = None  # K14's batch tile for this stack, asked of the extension once
         if disable_autograd_tracking:
             for p in self._net.parameters():

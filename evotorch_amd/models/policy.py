@@ -8,7 +8,9 @@ Reference parity: the `Policy` class of
 The parameters tensor may be 1-D (single member) or 2-D (population);
 2-D parameters run the whole population per step as a batched forward:
 one `ops.population_forward` launch (K13) for Linear/Tanh/ReLU stacks on a
-ROCm device, the vmapped `functional_call` for every other module.
+ROCm device, the vmapped `functional_call` for every other module. With
+`recurrent_kernel=True` a `MultiLayered` stack holding one RNN or LSTM
+layer takes one `ops.population_forward_recurrent` launch (K16) per step.
 """
 
 from typing import Any, Optional, Union
@@ -16,6 +18,7 @@ from typing import Any, Optional, Union
 import torch
 from torch import nn
 
+from .. import ops
 from .functional import make_functional_module
 from .parser import str_to_net
 
@@ -39,11 +42,16 @@ def reset_tensors(container: Any, mask: torch.Tensor) -> Any:
 
 
 class Policy:
-    def __init__(self, net: Union[str, nn.Module], **constants):
+    def __init__(self, net: Union[str, nn.Module], recurrent_kernel: bool = False, **constants):
+        """`recurrent_kernel=True` opts a recognised recurrent stack
+        (`functional.recurrent_stack_description`) with 2-D fp32 ROCm
+        parameters into `ops.population_forward_recurrent`; its results
+        differ from the vmapped path's in summation order only."""
         if isinstance(net, str):
             net = str_to_net(net, **constants)
         self._net = net
         self._fmodule = make_functional_module(net)
+        self._recurrent_kernel = bool(recurrent_kernel)
         self._params: Optional[torch.Tensor] = None
         self._state: Optional[Any] = None
 
@@ -82,6 +90,13 @@ class Policy:
     def __call__(self, obs: torch.Tensor) -> torch.Tensor:
         if self._params is None:
             raise RuntimeError("Call set_parameters first")
+        if self._recurrent_kernel and self._takes_recurrent_kernel(obs):
+            *stack, state_index = self._fmodule._recurrent_stack
+            state = None if self._state is None else self._state[state_index]
+            h, c = (state, None) if state is None or isinstance(state, torch.Tensor) else state
+            out, new_h, new_c = ops.population_forward_recurrent(self._params, obs, h, c, *stack)
+            self._state = {state_index: new_h if new_c is None else (new_h, new_c)}
+            return out
         if self._state is None:
             out = self._fmodule(self._params, obs)
         else:
@@ -91,6 +106,42 @@ class Policy:
             return y
         # probe: maybe the module is stateful but state was None
         return out
+
+    def _takes_recurrent_kernel(self, obs) -> bool:
+        """Whether this call is `ops.population_forward_recurrent`'s: a
+        recognised recurrent stack, 2-D fp32 ROCm parameters, `obs` fp32
+        (n, D0) on that device, no gradient asked for, the HIP path switched
+        on, and a state that is None or has the structure that path leaves:
+        `{state_index: h}` (RNN) or `{state_index: (h, c)}` (LSTM), fp32
+        (n, H) on the device."""
+        stack, params = self._fmodule._recurrent_stack, self._params
+        if stack is None or not isinstance(obs, torch.Tensor):
+            return False
+        if params.ndim != 2 or params.device.type != "cuda" or params.dtype != torch.float32:
+            return False
+        if params.shape[1] != self.parameter_count or obs.shape != (params.shape[0], stack[1][0]):
+            return False
+        if obs.device != params.device or obs.dtype != torch.float32:
+            return False
+        kinds, widths, _, _, state_index = stack
+        recurrent = next(i for i, kind in enumerate(kinds) if kind != 0)
+        parts = []
+        if self._state is not None:
+            if not isinstance(self._state, dict) or list(self._state) != [state_index]:
+                return False
+            state = self._state[state_index]
+            lstm = ops.POPULATION_FORWARD_KINDS[kinds[recurrent]] == "lstm"
+            parts = list(state) if lstm and isinstance(state, tuple) and len(state) == 2 else [state]
+            if len(parts) != (2 if lstm else 1):
+                return False
+            for t in parts:
+                if not isinstance(t, torch.Tensor) or t.shape != (params.shape[0], widths[recurrent + 1]):
+                    return False
+                if t.device != params.device or t.dtype != torch.float32:
+                    return False
+        if torch.is_grad_enabled() and any(t.requires_grad for t in [params, obs, *parts]):
+            return False  # the kernel has no backward
+        return ops.hip_for(params) is not None
 
     def _call_with_state(self, obs: torch.Tensor):
         if self._params.ndim == 2:

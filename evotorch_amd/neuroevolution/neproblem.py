@@ -39,7 +39,9 @@ class NEProblem(Problem):
         num_subbatches=None,
         subbatch_size=None,
         store_solution_stats: Optional[bool] = None,
+        recurrent_policy_kernel: bool = False,
     ):
+        self._recurrent_policy_kernel = bool(recurrent_policy_kernel)
         self._network_def = network
         self._network_args = dict(network_args or {})
         self._network_eval_func = network_eval_func
@@ -124,8 +126,10 @@ class NEProblem(Problem):
 
     def make_functional_policy(self) -> Policy:
         """A Policy over this problem's architecture for whole-population
-        batched forwards."""
-        return Policy(self._instantiate_net())
+        batched forwards. `recurrent_policy_kernel=True` at construction
+        opts recurrent stacks into `ops.population_forward_recurrent` (see
+        `Policy`)."""
+        return Policy(self._instantiate_net(), recurrent_kernel=self._recurrent_policy_kernel)
 
     # -- evaluation -----------------------------------------------------------
 

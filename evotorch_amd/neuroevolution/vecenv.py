@@ -166,6 +166,7 @@ class VecEnvNE(NEProblem):
         action_noise_stdev: Optional[float] = None,
         num_episodes: int = 1,
         use_hip_graph: bool = False,
+        recurrent_policy_kernel: bool = False,
         num_actors=None,
         num_gpus_per_actor=None,
         num_subbatches=None,
@@ -209,6 +210,7 @@ class VecEnvNE(NEProblem):
             device=device,
             seed=seed,
             store_solution_stats=False,
+            recurrent_policy_kernel=recurrent_policy_kernel,
             num_actors=num_actors,
             num_gpus_per_actor=num_gpus_per_actor,
             actor_config=actor_config,

@@ -17,7 +17,8 @@ K7 pareto_ranks / domination_counts, K9 mapelites_assign (routed from
 algorithms/mapelites.py), K10+K11 rollout_linear (called from
 neuroevolution/synthetic.py), K13 population_forward, K14
 population_forward_shared and K15 population_forward_shared_bf16 (routed
-from models/functional.py).
+from models/functional.py), K16 population_forward_recurrent (routed from
+models/policy.py).
 
 The launchers check every operand (ops/hip/check.h): dense, on the primary
 tensor's device, of its dtype and of exactly the length the kernel reads.
@@ -57,6 +58,8 @@ __all__ = [
     "population_forward",
     "population_forward_shared",
     "population_forward_shared_bf16",
+    "population_forward_recurrent",
+    "POPULATION_FORWARD_KINDS",
     "POPULATION_FORWARD_MAX_LAYERS",
     "POPULATION_FORWARD_MAX_WIDTH",
     "POPULATION_FORWARD_ACTIVATIONS",
@@ -671,6 +674,97 @@ def population_forward_shared_bf16(params: torch.Tensor, x: torch.Tensor, widths
         if name != "identity":
             h = getattr(torch, name)(h)
     return h
+
+
+# ============================================================================
+# K16 — population-batched step of a stack with one RNN or LSTM layer
+# ============================================================================
+
+POPULATION_FORWARD_KINDS = ("dense", "rnn", "lstm")  # the layer kind codes, by position
+
+
+def population_forward_recurrent(
+    params: torch.Tensor,
+    obs: torch.Tensor,
+    h: Optional[torch.Tensor],
+    c: Optional[torch.Tensor],
+    kinds,
+    widths,
+    activations,
+    has_bias: bool,
+) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """One step of every member's own recurrent network on its own
+    observation and state: `params` is (n, L), `obs` (n, widths[0]), `h`
+    (n, H) or None for "no state yet" (zeros), `c` (n, H) exactly when the
+    recurrent layer is an LSTM and `h` is given. Returns `(out, new_h,
+    new_c)`, `new_c` None for an RNN; the inputs are never written.
+
+    `kinds[i]` indexes POPULATION_FORWARD_KINDS; exactly one layer is
+    recurrent and H is its output width. Row m of `params` follows
+    `named_parameters()` order: a dense layer as in `population_forward`
+    (`has_bias` is the dense layers'), an RNN layer as W_ih (H x K), W_hh
+    (H x H), b_ih, b_hh with `activations[i]` tanh or relu, an LSTM layer
+    as W_ih (4H x K), W_hh (4H x H), b_ih, b_hh with gate blocks i, f, g, o
+    and `activations[i]` identity.
+
+    fp32 ROCm tensors take ONE kernel launch
+    (ops/hip/policy_forward_recurrent.hip), on the current stream and
+    without a host sync (hipGraph-capturable); a member's results do not
+    depend on the rest of the population. CPU tensors, other dtypes, and
+    ROCm tensors under `eager_on_gpu()` run the eager chain below with the
+    formulas of `models.layers.RNN` / `LSTM`; in float64 it is the
+    kernel's oracle."""
+    widths, activations = _stack_description(widths, activations)
+    kinds = [int(k) for k in kinds]
+    if len(kinds) != len(activations) or sorted(kinds)[:-1] != [0] * (len(kinds) - 1) or max(kinds) not in (1, 2):
+        raise ValueError(f"expected one kind per layer and exactly one recurrent layer, got kinds={kinds}")
+    lstm = POPULATION_FORWARD_KINDS[max(kinds)] == "lstm"
+    if params.ndim != 2 or obs.shape != (params.shape[0], widths[0]):
+        raise ValueError(f"expected params (n, L) and obs (n, {widths[0]}), got {tuple(params.shape)} and {tuple(obs.shape)}")
+    mod = hip_for(params) if params.dtype == torch.float32 else None
+    if mod is not None:
+        state = [None if t is None else _dense(params, t)[0] for t in (h, c)]
+        out, new_h, new_c = mod.population_recurrent_forward(
+            params.contiguous(), *_dense(params, obs), *state, kinds, widths, activations, bool(has_bias)
+        )
+        return out, new_h, (new_c if lstm else None)
+    n, x, offset = params.shape[0], obs, 0
+    new_h = new_c = None
+
+    def take(rows, cols=None):
+        nonlocal offset
+        count = rows * (cols or 1)
+        t = params[:, offset : offset + count]
+        offset += count
+        return t if cols is None else t.reshape(n, rows, cols)
+
+    for k, j, act, kind in zip(widths[:-1], widths[1:], activations, kinds):
+        name = POPULATION_FORWARD_ACTIVATIONS[act]
+        if POPULATION_FORWARD_KINDS[kind] == "dense":
+            x = torch.einsum("nk,njk->nj", x, take(j, k))
+            if has_bias:
+                x = x + take(j)
+            if name != "identity":
+                x = getattr(torch, name)(x)
+            continue
+        rows = 4 * j if POPULATION_FORWARD_KINDS[kind] == "lstm" else j
+        W_ih, W_hh, b_ih, b_hh = take(rows, k), take(rows, j), take(rows), take(rows)
+        h_in = x.new_zeros(n, j) if h is None else h
+        z = torch.einsum("nk,njk->nj", x, W_ih) + b_ih + torch.einsum("nk,njk->nj", h_in, W_hh) + b_hh
+        if rows == j:
+            if name not in ("tanh", "relu"):
+                raise ValueError(f"an RNN layer's activation is tanh or relu, got {name}")
+            new_h = getattr(torch, name)(z)
+        else:
+            if (c is None) != (h is None):
+                raise ValueError("c must be given exactly when the recurrent layer is an LSTM and h is given")
+            gi, gf, gg, go = z.split(j, dim=-1)
+            new_c = torch.sigmoid(gf) * (torch.zeros_like(h_in) if c is None else c) + torch.sigmoid(gi) * torch.tanh(gg)
+            new_h = torch.sigmoid(go) * torch.tanh(new_c)
+        x = new_h
+    if offset != params.shape[1]:
+        raise ValueError(f"this stack takes {offset} parameters per member, got {params.shape[1]}")
+    return x, new_h, new_c
 
 
 # ============================================================================

@@ -35,6 +35,9 @@ torch::Tensor population_mlp_forward_shared_bf16(torch::Tensor params, torch::Te
                                                  std::vector<int64_t> activations, bool has_bias,
                                                  int64_t batch_tile);
 int64_t population_mlp_forward_shared_bf16_batch_tile(std::vector<int64_t> widths);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> population_recurrent_forward(
+    torch::Tensor params, torch::Tensor obs, c10::optional<torch::Tensor> h, c10::optional<torch::Tensor> c,
+    std::vector<int64_t> kinds, std::vector<int64_t> widths, std::vector<int64_t> activations, bool has_bias);
 torch::Tensor rollout_linear(torch::Tensor params, torch::Tensor env_blob, torch::Tensor obs_stats_out,
                              int64_t obs_dim, int64_t act_dim, int64_t rank, int64_t steps, double alive_bonus,
                              double act_cost, int64_t init_seed, int64_t member_offset, int64_t policy_hidden,
@@ -106,6 +109,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("batch_tile") = 0);
     m.def("population_mlp_forward_shared_bf16_batch_tile", &ea::population_mlp_forward_shared_bf16_batch_tile,
           "K15: rows per batch tile (32 or 64) the kernel takes for these widths (host only)", py::arg("widths"));
+    m.def("population_recurrent_forward", &ea::population_recurrent_forward,
+          "K16: one step of a stack of 1-4 weighted layers (kinds 0 dense, 1 RNN, 2 LSTM; exactly one recurrent) for "
+          "every member's own flat parameter vector and state; h (and c for an LSTM) may be None for no state yet; "
+          "fp32, returns (out [n, widths[-1]], new_h [n, H], new_c [n, H] or empty)",
+          py::arg("params"), py::arg("obs"), py::arg("h"), py::arg("c"), py::arg("kinds"), py::arg("widths"),
+          py::arg("activations"), py::arg("has_bias"));
     // Both rollout entry points take `obs_stats_out` either as one tensor, to
     // which the summed statistics are ADDED and a fresh fitness tensor is
     // returned, or as a pair (obs_stats_out, fitness_out) of plain outputs:

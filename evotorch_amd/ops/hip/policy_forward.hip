@@ -70,76 +70,6 @@ struct PolicyForwardArgs {
     int group[kMaxLayers];  // lanes per row group: 8, 16 or 64
 };
 
-// Sum over each group of G lanes, valid in the group's LAST lane.
-template <int G>
-__device__ __forceinline__ float group_sum(float x) {
-    if constexpr (G == 8) {
-        return group8_sum_dpp(x);
-    } else {
-        x = dpp_add<0x111>(x);  // row_shr:1
-        x = dpp_add<0x112>(x);  // row_shr:2
-        x = dpp_add<0x114>(x);  // row_shr:4
-        x = dpp_add<0x118>(x);  // row_shr:8: lane 15 of each 16-lane row
-        if constexpr (G == 64) {
-            // rows 0..3 in lane order: ((r0 + r1) + r2) + r3, read on the scalar pipe
-            const int xi = __builtin_bit_cast(int, x);
-            const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 15));
-            const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 31));
-            const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 47));
-            x = ((r0 + r1) + r2) + x;  // lane 63 holds r3
-        }
-        return x;
-    }
-}
-
-// Orders this wave's LDS stores before its later LDS loads (other lanes' data).
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// One layer of one member: y[0:N) = act(W [N][K] · x[0:K) + b). x is in LDS;
-// y is LDS or global. Runs with all 64 lanes active.
-template <int G>
-__device__ __forceinline__ void policy_layer(const float* __restrict__ W, const float* __restrict__ b,
-                                             const float* x, float* y, int K, int N, int act, int lane) {
-    constexpr int kRowsPerPass = kWaveSize / G;
-    const int gl = lane & (G - 1);
-    const int group = lane / G;
-    const int words = K >> 2;                 // whole 16-byte words of a row
-    const int steps = (words + G - 1) / G;    // wave-uniform trip count
-    const int tail = K & 3;
-    const floatx4* x4 = reinterpret_cast<const floatx4*>(x);
-    for (int row0 = 0; row0 < N; row0 += kRowsPerPass) {
-        const int row = row0 + group;
-        const float* Wr = W + (long)min(row, N - 1) * K;
-        float acc = 0.0f;
-#pragma unroll 4
-        for (int s = 0; s < steps; ++s) {
-            const int w = gl + s * G;
-            const bool in = w < words;
-            const int wc = in ? w : 0;  // words >= 1 here, so word 0 is inside the row
-            const floatx4_a4 wv = *reinterpret_cast<const floatx4_a4*>(Wr + 4 * wc);
-            const floatx4 xv = x4[wc];
-            float t = fmaf(wv.x, xv.x, acc);
-            t = fmaf(wv.y, xv.y, t);
-            t = fmaf(wv.z, xv.z, t);
-            t = fmaf(wv.w, xv.w, t);
-            acc = in ? t : acc;
-        }
-        if (gl < tail) {  // G >= 8 > 3: one trailing element per lane
-            const int k = 4 * words + gl;
-            acc = fmaf(Wr[k], x[k], acc);
-        }
-        acc = group_sum<G>(acc);
-        if (gl == G - 1 && row < N) {
-            if (b != nullptr) acc += b[row];
-            y[row] = policy_activation(acc, act);
-        }
-    }
-}
-
 __global__ __launch_bounds__(kMembersPerBlock* kWaveSize) void population_mlp_forward_kernel(PolicyForwardArgs args) {
     // [wave][ping-pong][kMaxWidth]; 16-byte aligned for the ds_read_b128 of the inputs
     __shared__ __attribute__((aligned(16))) float lds[kMembersPerBlock][2][kMaxWidth];
@@ -182,17 +112,6 @@ __global__ __launch_bounds__(kMembersPerBlock* kWaveSize) void population_mlp_fo
             nxt = t;
         }
     }
-}
-
-// Lanes per row group of a layer with K inputs: the narrowest group whose
-// lanes make at most 2 (G = 8) or 8 (G = 16) steps along the row. K = 3
-// leaves 7 of 8 lanes idle instead of 63 of 64; K = 376 (94 words) runs
-// 6 steps on four rows at once; only K > 512 spreads a row over the wave.
-static int policy_group_width(int K) {
-    const int words = K / 4;
-    if (words <= 2 * 8) return 8;
-    if (words <= 8 * 16) return 16;
-    return 64;
 }
 
 torch::Tensor population_mlp_forward(torch::Tensor params, torch::Tensor obs, std::vector<int64_t> widths,

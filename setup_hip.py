@@ -26,6 +26,7 @@ setup(
                 os.path.join(SRC, "es_kernels.hip"),
                 os.path.join(SRC, "obsnorm.hip"),
                 os.path.join(SRC, "policy_forward.hip"),
+                os.path.join(SRC, "policy_forward_recurrent.hip"),
                 os.path.join(SRC, "policy_forward_shared.hip"),
                 os.path.join(SRC, "policy_forward_shared_bf16.hip"),
                 os.path.join(SRC, "rollout.hip"),
