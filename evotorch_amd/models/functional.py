@@ -13,7 +13,9 @@ one shared minibatch (`forward_shared`, SupervisedNE's evaluation) is a
 GEMM chain per member on fp32 MFMA, `ops.population_forward_shared` (K14,
 ops/hip/policy_forward_shared.hip), or on request on bf16 MFMA,
 `ops.population_forward_shared_bf16` (K15,
-ops/hip/policy_forward_shared_bf16.hip). A `MultiLayered` stack with one
+ops/hip/policy_forward_shared_bf16.hip); `loss_shared` reduces either to
+each member's mean MSE or cross-entropy in the same launch,
+`ops.population_loss_shared` (K17, ops/hip/policy_loss.h). A `MultiLayered` stack with one
 `RNN` or `LSTM` layer is recognised too (`recurrent_stack_description`);
 `models.Policy` runs its step as one launch,
 `ops.population_forward_recurrent` (K16,
@@ -156,6 +158,7 @@ class ModuleExpectingFlatParameters:
         self._dense_stack = dense_stack_description(self._net)
         self._recurrent_stack = recurrent_stack_description(self._net)  # K16's, taken by models.Policy on request
         self._shared_tile = None  # K14's batch tile for this stack, asked of the extension once
+        self._loss_tile = None  # K17's, for the fp32 loss layout
         if disable_autograd_tracking:
             for p in self._net.parameters():
                 p.requires_grad_(False)
@@ -238,6 +241,42 @@ class ModuleExpectingFlatParameters:
                 return ops.population_forward_shared_bf16(flat_params, x, *self._dense_stack)
             return ops.population_forward_shared(flat_params, x, *self._dense_stack)
         return torch.func.vmap(self._single, in_dims=(0, None))(flat_params, x)
+
+    def takes_loss_kernel(self, flat_params: torch.Tensor, x, y, loss: str, precision: str = "fp32") -> bool:
+        """Whether `loss_shared(flat_params, x, y, loss, precision)` is one
+        launch of `ops.population_loss_shared`'s kernel: everything
+        `takes_shared_kernel` asks (for "fp32" the tile rule is asked of
+        the loss layout, whose rows also hold the last layer's output), and
+        a `y` the kernel reads as it is: fp32 of shape exactly
+        (B, D_last) for "mse" (no broadcasting case), int64 class indices
+        of shape (B,) for "cross_entropy", on the parameters' device."""
+        if loss not in ops.POPULATION_LOSS_KINDS:
+            raise ValueError(f"loss must be one of {ops.POPULATION_LOSS_KINDS}, got {loss!r}")
+        if not self.takes_shared_kernel(flat_params, x, precision) or not isinstance(y, torch.Tensor):
+            return False
+        if y.device != flat_params.device or y.requires_grad:
+            return False
+        if loss == "mse":
+            if y.dtype != torch.float32 or y.shape != (x.shape[0], self._dense_stack[0][-1]):
+                return False
+        elif y.dtype != torch.int64 or y.shape != (x.shape[0],):
+            return False
+        if precision == "bf16":
+            return True
+        if self._loss_tile is None:
+            self._loss_tile = ops.hip_for(flat_params).population_mlp_loss_shared_batch_tile(self._dense_stack[0], False)
+        return self._loss_tile >= ops.POPULATION_FORWARD_SHARED_MIN_TILE
+
+    def loss_shared(self, flat_params: torch.Tensor, x: torch.Tensor, y: torch.Tensor, loss: str, precision: str = "fp32") -> torch.Tensor:
+        """The mean `loss` ("mse" or "cross_entropy") of every member of
+        the 2-D `flat_params` (n, L) on the same minibatch `(x, y)`: (n,).
+        One `ops.population_loss_shared` launch for forward and loss
+        together where `takes_loss_kernel` holds; else `forward_shared`
+        followed by the torch loss per member."""
+        if self.takes_loss_kernel(flat_params, x, y, loss, precision):
+            return ops.population_loss_shared(flat_params, x, y, *self._dense_stack, loss=loss, precision=precision)
+        loss_func = torch.nn.functional.mse_loss if loss == "mse" else torch.nn.functional.cross_entropy
+        return torch.func.vmap(lambda p: loss_func(p, y))(self.forward_shared(flat_params, x, precision))
 
     def __call__(self, flat_params: torch.Tensor, *inputs):
         if flat_params.ndim == 1:

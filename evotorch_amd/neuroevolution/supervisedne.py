@@ -11,7 +11,11 @@ batched forward when `vectorized_eval=True` (default for
 common_minibatch mode): one fp32-MFMA kernel launch for a dense stack on
 a 2-D fp32 ROCm minibatch (`forward_shared`, K14; with
 `forward_precision="bf16"` one bf16-MFMA launch, K15, for stacks of any
-width), vmapped (rocBLAS batched GEMMs) otherwise.
+width), vmapped (rocBLAS batched GEMMs) otherwise. Where the loss is
+`nn.MSELoss()`, `nn.CrossEntropyLoss()` (both at their defaults) or
+`torch.nn.functional.cross_entropy` and the targets fit, that launch
+also reduces the predictions to each member's loss (`loss_shared`, K17):
+the predictions never reach memory and no loss launches follow.
 """
 
 from typing import Callable, Optional, Union
@@ -139,6 +143,27 @@ class SupervisedNE(NEProblem):
         with torch.no_grad():
             return self._loss(network(x), y)
 
+    def _fused_loss_kind(self) -> Optional[str]:
+        """The `ops.POPULATION_LOSS_KINDS` name of this problem's loss where
+        the fused kernel computes exactly it, else None. Recognised: an
+        `nn.MSELoss` with the mean reduction, an `nn.CrossEntropyLoss` at
+        its defaults, the function `torch.nn.functional.cross_entropy`;
+        subclasses, lambdas and an overridden `_loss` are not.
+        `torch.nn.functional.mse_loss` passed as the bare function keeps
+        the separate forward and loss launches, whose bits the K14 and K15
+        routing tests pin."""
+        if type(self)._loss is not SupervisedNE._loss:
+            return None
+        f = self._loss_func
+        if type(f) is nn.MSELoss and f.reduction == "mean":
+            return "mse"
+        if f is nn.functional.cross_entropy:
+            return "cross_entropy"
+        if type(f) is nn.CrossEntropyLoss:
+            if f.reduction == "mean" and f.weight is None and f.ignore_index == -100 and f.label_smoothing == 0:
+                return "cross_entropy"
+        return None
+
     # -- evaluation ----------------------------------------------------------
 
     def _evaluate_network(self, network: nn.Module) -> torch.Tensor:
@@ -165,7 +190,8 @@ class SupervisedNE(NEProblem):
         sub = self._subbatch_size
         if sub is None and self._num_subbatches is not None:
             sub = max(1, (n + self._num_subbatches - 1) // self._num_subbatches)
-        losses = torch.zeros(n, dtype=torch.float32, device=self.network_device)
+        losses = None  # summed over the minibatches; allocated by the first chunk that needs it
+        fused_kind = self._fused_loss_kind()
         # population_forward protocol: a net may provide its own
         # population-batched forward `population_forward(params (G, P),
         # x) -> (G, N, *out)` — e.g. convnets mapping member weights onto
@@ -183,6 +209,14 @@ class SupervisedNE(NEProblem):
                     if pop_fwd is not None:
                         preds = pop_fwd(params[start:stop], x)
                         chunk = torch.func.vmap(lambda p: self._loss(p, y))(preds)
+                    elif fused_kind is not None and self._fmodule.takes_loss_kernel(
+                        params[start:stop], x, y, fused_kind, self._forward_precision
+                    ):
+                        # forward and loss in one K17 launch (one more for the tile sums when the minibatch exceeds a tile)
+                        chunk = self._fmodule.loss_shared(params[start:stop], x, y, fused_kind, self._forward_precision)
+                        if self._num_minibatches == 1 and stop - start == n:
+                            batch.set_evals(chunk.to(batch.device))  # the whole evaluation: nothing to add or divide
+                            return
                     elif self._fmodule.takes_shared_kernel(params[start:stop], x, self._forward_precision):
                         # dense stack on a 2-D fp32 ROCm minibatch: one K14 launch, or one K15 launch for "bf16"
                         forward = ops.population_forward_shared_bf16 if self._forward_precision == "bf16" else ops.population_forward_shared
@@ -193,5 +227,9 @@ class SupervisedNE(NEProblem):
                             return self._loss(self._fmodule._single(flat, x), y)
 
                         chunk = torch.func.vmap(member_loss, randomness="different")(params[start:stop])
+                    if losses is None:
+                        losses = torch.zeros(n, dtype=torch.float32, device=self.network_device)
                     losses[start:stop] = losses[start:stop] + chunk
+        if losses is None:  # an empty batch
+            losses = torch.zeros(n, dtype=torch.float32, device=self.network_device)
         batch.set_evals((losses / self._num_minibatches).to(batch.device))

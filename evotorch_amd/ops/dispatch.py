@@ -18,7 +18,8 @@ algorithms/mapelites.py), K10+K11 rollout_linear (called from
 neuroevolution/synthetic.py), K13 population_forward, K14
 population_forward_shared and K15 population_forward_shared_bf16 (routed
 from models/functional.py), K16 population_forward_recurrent (routed from
-models/policy.py).
+models/policy.py), K17 population_loss_shared (routed from
+neuroevolution/supervisedne.py).
 
 The launchers check every operand (ops/hip/check.h): dense, on the primary
 tensor's device, of its dtype and of exactly the length the kernel reads.
@@ -64,6 +65,8 @@ __all__ = [
     "POPULATION_FORWARD_MAX_WIDTH",
     "POPULATION_FORWARD_ACTIVATIONS",
     "POPULATION_FORWARD_SHARED_MIN_TILE",
+    "population_loss_shared",
+    "POPULATION_LOSS_KINDS",
 ]
 
 
@@ -674,6 +677,58 @@ def population_forward_shared_bf16(params: torch.Tensor, x: torch.Tensor, widths
         if name != "identity":
             h = getattr(torch, name)(h)
     return h
+
+
+# ============================================================================
+# K17 — the shared-minibatch forward with the mean loss fused into its epilogue
+# ============================================================================
+
+POPULATION_LOSS_KINDS = ("mse", "cross_entropy")  # the loss kind codes, by position
+
+
+def population_loss_shared(
+    params: torch.Tensor, x: torch.Tensor, y: torch.Tensor, widths, activations, has_bias: bool, loss: str = "mse", precision: str = "fp32"
+) -> torch.Tensor:
+    """The mean loss of every member's dense network on the SAME minibatch
+    `(x, y)`: `params` is (n, L), `x` (B, widths[0]), the result (n,).
+    The stack description and the layout of a `params` row are those of
+    `population_forward`. `loss="mse"` takes `y` (B, widths[-1]) and is
+    `torch.nn.functional.mse_loss` per member; `loss="cross_entropy"` takes
+    int64 class indices `y` (B,) and is `torch.nn.functional.cross_entropy`
+    per member, targets of -100 ignored as there. `precision="bf16"` takes
+    `population_forward_shared_bf16`'s forward.
+
+    fp32 ROCm tensors take ONE kernel launch for forward and loss together
+    (ops/hip/policy_loss.h in the last epilogue of K14 or K15; one
+    reduction more when B exceeds the kernel's batch tile), on the current
+    stream and without a host sync (hipGraph-capturable); the predictions
+    never reach memory, and `loss[m]` depends bit for bit on `params[m]`,
+    `x`, `y` and the stack description only. CPU tensors, other dtypes, and
+    ROCm tensors under `eager_on_gpu()` run the eager chain below; in
+    float64 it is the kernel's oracle."""
+    widths, activations = _stack_description(widths, activations)
+    if loss not in POPULATION_LOSS_KINDS:
+        raise ValueError(f"loss must be one of {POPULATION_LOSS_KINDS}, got {loss!r}")
+    if precision not in ("fp32", "bf16"):
+        raise ValueError(f'precision must be "fp32" or "bf16", got {precision!r}')
+    if params.ndim != 2 or x.ndim != 2 or x.shape[1] != widths[0]:
+        raise ValueError(f"expected params (n, L) and x (B, {widths[0]}), got {tuple(params.shape)} and {tuple(x.shape)}")
+    y_shape = (x.shape[0], widths[-1]) if loss == "mse" else (x.shape[0],)
+    if tuple(y.shape) != y_shape:
+        raise ValueError(f"expected y {y_shape} for loss={loss!r}, got {tuple(y.shape)}")
+    mod = hip_for(params) if params.dtype == torch.float32 else None
+    if mod is not None:
+        y = _dense(params, y)[0] if loss == "mse" else y.contiguous()
+        return mod.population_mlp_loss_shared(
+            params.contiguous(), *_dense(params, x), y, widths, activations, bool(has_bias), POPULATION_LOSS_KINDS.index(loss), precision == "bf16"
+        )
+    forward = population_forward_shared_bf16 if precision == "bf16" else population_forward_shared
+    preds = forward(params, x, widths, activations, has_bias)
+    if loss == "mse":
+        member_losses = [torch.nn.functional.mse_loss(p, y.to(p.dtype)) for p in preds]
+    else:
+        member_losses = [torch.nn.functional.cross_entropy(p, y) for p in preds]
+    return torch.stack(member_losses) if member_losses else preds.new_empty(0)
 
 
 # ============================================================================

@@ -35,6 +35,10 @@ torch::Tensor population_mlp_forward_shared_bf16(torch::Tensor params, torch::Te
                                                  std::vector<int64_t> activations, bool has_bias,
                                                  int64_t batch_tile);
 int64_t population_mlp_forward_shared_bf16_batch_tile(std::vector<int64_t> widths);
+torch::Tensor population_mlp_loss_shared(torch::Tensor params, torch::Tensor x, torch::Tensor y,
+                                         std::vector<int64_t> widths, std::vector<int64_t> activations, bool has_bias,
+                                         int64_t loss_kind, bool bf16);
+int64_t population_mlp_loss_shared_batch_tile(std::vector<int64_t> widths, bool bf16);
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> population_recurrent_forward(
     torch::Tensor params, torch::Tensor obs, c10::optional<torch::Tensor> h, c10::optional<torch::Tensor> c,
     std::vector<int64_t> kinds, std::vector<int64_t> widths, std::vector<int64_t> activations, bool has_bias);
@@ -109,6 +113,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("batch_tile") = 0);
     m.def("population_mlp_forward_shared_bf16_batch_tile", &ea::population_mlp_forward_shared_bf16_batch_tile,
           "K15: rows per batch tile (32 or 64) the kernel takes for these widths (host only)", py::arg("widths"));
+    m.def("population_mlp_loss_shared", &ea::population_mlp_loss_shared,
+          "K17: K14's (or with bf16, K15's) forward on the shared minibatch x [B, widths[0]] with the mean loss fused "
+          "into the last epilogue: loss_kind 0 is MSE against y fp32 [B, widths[-1]], 1 is cross-entropy against "
+          "y int64 [B] (targets of -100 are ignored, as torch's default); fp32, returns [n]",
+          py::arg("params"), py::arg("x"), py::arg("y"), py::arg("widths"), py::arg("activations"),
+          py::arg("has_bias"), py::arg("loss_kind"), py::arg("bf16") = false);
+    m.def("population_mlp_loss_shared_batch_tile", &ea::population_mlp_loss_shared_batch_tile,
+          "K17: rows per batch tile the loss kernel takes for these widths (host only)", py::arg("widths"),
+          py::arg("bf16") = false);
     m.def("population_recurrent_forward", &ea::population_recurrent_forward,
           "K16: one step of a stack of 1-4 weighted layers (kinds 0 dense, 1 RNN, 2 LSTM; exactly one recurrent) for "
           "every member's own flat parameter vector and state; h (and c for an LSTM) may be None for no state yet; "

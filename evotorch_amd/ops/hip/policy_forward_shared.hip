@@ -55,12 +55,18 @@
 // k order is a fixed function of K, and BT depends on the widths only, so
 // neither n, B, the row's place in its tile nor the other members matter.
 // No atomics; all stores are plain vector stores.
+//
+// K17 (kLoss): the last layer stores its tile to the other LDS buffer instead
+// of `out`, and after one barrier the loss phase of policy_loss.h reduces it
+// to the member's loss. Up to that store the arithmetic is the same code, so
+// the loss is taken of the bits the kLoss = false kernel stores.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
 #include "check.h"
 #include "policy_common.h"
+#include "policy_loss.h"
 #include "rollout_common.h"
 
 namespace ea {
@@ -87,8 +93,19 @@ __host__ __device__ inline size_t shared_lds_bytes(const int* width, int layers,
     return (size_t)bt * (shared_stride(width, layers, 0) + shared_stride(width, layers, 1)) * sizeof(float);
 }
 
-template <int BT>
-__global__ __launch_bounds__(kSharedThreads) void population_mlp_forward_shared_kernel(SharedForwardArgs args) {
+// The loss layout (K17) is the same rule with the last layer's output counted
+// as one more row to hold: buffer layers & 1 also fits width[layers].
+__host__ __device__ inline int shared_loss_stride(const int* width, int layers, int parity) {
+    return shared_stride(width, layers + 1, parity);
+}
+
+__host__ __device__ inline size_t shared_loss_lds_bytes(const int* width, int layers, int bt) {
+    return shared_lds_bytes(width, layers + 1, bt);
+}
+
+template <int BT, bool kLoss>
+__global__ __launch_bounds__(kSharedThreads) void population_mlp_forward_shared_kernel(SharedForwardArgs args,
+                                                                                       SharedLossArgs largs) {
     constexpr int kRowTiles = BT / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char shared_lds[];
     // grid block -> logical block: XCD x takes the logical blocks [x * per_xcd, (x + 1) * per_xcd)
@@ -98,7 +115,8 @@ __global__ __launch_bounds__(kSharedThreads) void population_mlp_forward_shared_
     const int m = logical / args.tiles;
     const int b0 = (logical - m * args.tiles) * BT;
 
-    const int stride0 = shared_stride(args.width, args.layers, 0), stride1 = shared_stride(args.width, args.layers, 1);
+    const int stride0 = kLoss ? shared_loss_stride(args.width, args.layers, 0) : shared_stride(args.width, args.layers, 0);
+    const int stride1 = kLoss ? shared_loss_stride(args.width, args.layers, 1) : shared_stride(args.width, args.layers, 1);
     float* const buf0 = reinterpret_cast<float*>(shared_lds);
     float* const buf1 = buf0 + BT * stride0;
     const int tid = threadIdx.x;
@@ -173,8 +191,12 @@ __global__ __launch_bounds__(kSharedThreads) void population_mlp_forward_shared_
                     if (bias != nullptr) v += bv;
                     v = policy_activation(v, act);
                     if (last) {
-                        const int b = b0 + row;
-                        if (b < args.B && col < N) args.out[((long)m * args.B + b) * N + col] = v;
+                        if constexpr (kLoss) {
+                            if (col < N) nxt[row * ns + col] = v;
+                        } else {
+                            const int b = b0 + row;
+                            if (b < args.B && col < N) args.out[((long)m * args.B + b) * N + col] = v;
+                        }
                     } else {
                         nxt[row * ns + col] = col < N ? v : 0.0f;
                     }
@@ -182,6 +204,11 @@ __global__ __launch_bounds__(kSharedThreads) void population_mlp_forward_shared_
             }
         }
         if (!last) __syncthreads();
+    }
+    if constexpr (kLoss) {
+        __syncthreads();
+        const bool odd = args.layers & 1;  // the buffer the last layer stored to
+        shared_loss_phase<BT>(odd ? buf1 : buf0, odd ? stride1 : stride0, odd ? buf0 : buf1, m, b0 / BT, args, largs);
     }
 }
 
@@ -194,6 +221,9 @@ static int shared_batch_tile(const int* width, int layers) {
     return 16;
 }
 
+// The same rule asked of the loss layout.
+int shared_loss_batch_tile(const int* width, int layers) { return shared_batch_tile(width, layers + 1); }
+
 // What the router asks (models/functional.py sends only stacks with tiles of
 // 32 rows or more here: with 16-row tiles the kernel measured slower than
 // the batched-GEMM path, see docs/kernels.md).
@@ -204,16 +234,29 @@ int64_t population_mlp_forward_shared_batch_tile(std::vector<int64_t> widths) {
     return shared_batch_tile(width, (int)widths.size() - 1);
 }
 
-template <int BT>
-static void launch_shared(const SharedForwardArgs& args, size_t lds_bytes, hipStream_t stream) {
+template <int BT, bool kLoss>
+static void launch_shared(const SharedForwardArgs& args, const SharedLossArgs& largs, size_t lds_bytes,
+                          hipStream_t stream) {
     static bool attr_set = false;
     if (!attr_set) {
-        allow_max_dynamic_lds(reinterpret_cast<const void*>(&population_mlp_forward_shared_kernel<BT>));
+        allow_max_dynamic_lds(reinterpret_cast<const void*>(&population_mlp_forward_shared_kernel<BT, kLoss>));
         attr_set = true;
     }
     const int grid = (args.blocks + kXcds - 1) / kXcds * kXcds;
-    hipLaunchKernelGGL(population_mlp_forward_shared_kernel<BT>, dim3(grid), dim3(kSharedThreads), lds_bytes, stream,
-                       args);
+    hipLaunchKernelGGL((population_mlp_forward_shared_kernel<BT, kLoss>), dim3(grid), dim3(kSharedThreads), lds_bytes,
+                       stream, args, largs);
+}
+
+// K17's launch: `args` as for the forward (out unused), `bt` from shared_loss_batch_tile.
+void launch_shared_loss(const SharedForwardArgs& args, const SharedLossArgs& largs, int bt, hipStream_t stream) {
+    const size_t lds_bytes = shared_loss_lds_bytes(args.width, args.layers, bt);
+    if (bt == 64) {
+        launch_shared<64, true>(args, largs, lds_bytes, stream);
+    } else if (bt == 32) {
+        launch_shared<32, true>(args, largs, lds_bytes, stream);
+    } else {
+        launch_shared<16, true>(args, largs, lds_bytes, stream);
+    }
 }
 
 torch::Tensor population_mlp_forward_shared(torch::Tensor params, torch::Tensor x, std::vector<int64_t> widths,
@@ -246,12 +289,13 @@ torch::Tensor population_mlp_forward_shared(torch::Tensor params, torch::Tensor 
     args.has_bias = has_bias ? 1 : 0;
     const size_t lds_bytes = shared_lds_bytes(args.width, args.layers, bt);
     auto stream = at::cuda::getCurrentCUDAStream();
+    const SharedLossArgs no_loss{};
     if (bt == 64) {
-        launch_shared<64>(args, lds_bytes, stream);
+        launch_shared<64, false>(args, no_loss, lds_bytes, stream);
     } else if (bt == 32) {
-        launch_shared<32>(args, lds_bytes, stream);
+        launch_shared<32, false>(args, no_loss, lds_bytes, stream);
     } else {
-        launch_shared<16>(args, lds_bytes, stream);
+        launch_shared<16, false>(args, no_loss, lds_bytes, stream);
     }
     return out;
 }

@@ -60,12 +60,18 @@
 // description alone: row i of an MFMA result depends on row i of A only, the
 // k order is a fixed function of K, BT depends on the widths only. No
 // atomics; all stores are plain vector stores; current stream, no host sync.
+//
+// K17 (kLoss): the last layer stores its unrounded fp32 tile to the other LDS
+// buffer, whose rows are long enough for it (bf16_loss_stride), instead of
+// `out`, and after one barrier the loss phase of policy_loss.h reduces it to
+// the member's loss: the loss of the bits the kLoss = false kernel stores.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
 #include "check.h"
 #include "policy_common.h"
+#include "policy_loss.h"
 #include "rollout_common.h"
 
 namespace ea {
@@ -91,8 +97,22 @@ __host__ __device__ inline size_t bf16_lds_bytes(const int* width, int layers, i
     return (size_t)bt * (bf16_stride(width, layers, 0) + bf16_stride(width, layers, 1)) * sizeof(__bf16);
 }
 
-template <int BT>
-__global__ __launch_bounds__(kBf16Threads) void population_mlp_forward_shared_bf16_kernel(SharedForwardArgs args) {
+// The loss layout (K17): buffer layers & 1 also holds the last layer's output
+// as one fp32 row of width[layers], i.e. 2 * width[layers] bf16 slots, padded
+// by the same rule (rows stay 64a + 16 bytes, so 16-byte aligned).
+__host__ __device__ inline int bf16_loss_stride(const int* width, int layers, int parity) {
+    const int s = bf16_stride(width, layers, parity);
+    const int row = ((2 * width[layers] + 31) & ~31) + 8;
+    return parity == (layers & 1) && row > s ? row : s;
+}
+
+__host__ __device__ inline size_t bf16_loss_lds_bytes(const int* width, int layers, int bt) {
+    return (size_t)bt * (bf16_loss_stride(width, layers, 0) + bf16_loss_stride(width, layers, 1)) * sizeof(__bf16);
+}
+
+template <int BT, bool kLoss>
+__global__ __launch_bounds__(kBf16Threads) void population_mlp_forward_shared_bf16_kernel(SharedForwardArgs args,
+                                                                                          SharedLossArgs largs) {
     constexpr int kRowTiles = BT / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char bf16_lds[];
     // grid block -> logical block: XCD x takes the logical blocks [x * per_xcd, (x + 1) * per_xcd)
@@ -102,7 +122,8 @@ __global__ __launch_bounds__(kBf16Threads) void population_mlp_forward_shared_bf
     const int m = logical / args.tiles;
     const int b0 = (logical - m * args.tiles) * BT;
 
-    const int stride0 = bf16_stride(args.width, args.layers, 0), stride1 = bf16_stride(args.width, args.layers, 1);
+    const int stride0 = kLoss ? bf16_loss_stride(args.width, args.layers, 0) : bf16_stride(args.width, args.layers, 0);
+    const int stride1 = kLoss ? bf16_loss_stride(args.width, args.layers, 1) : bf16_stride(args.width, args.layers, 1);
     __bf16* const buf0 = reinterpret_cast<__bf16*>(bf16_lds);
     __bf16* const buf1 = buf0 + BT * stride0;
     const int tid = threadIdx.x;
@@ -204,7 +225,13 @@ __global__ __launch_bounds__(kBf16Threads) void population_mlp_forward_shared_bf
                 for (int r = 0; r < 4; r += 2) {
                     const int row = t * 16 + 4 * g + r;
                     floatx2 v = {policy_activation(acc[t][r], act), policy_activation(acc[t][r + 1], act)};
-                    if (last) {
+                    if (last && kLoss) {
+                        if (col < N) {  // fp32 rows of ns / 2 floats in the other buffer
+                            float* tile = reinterpret_cast<float*>(nxt);
+                            tile[row * (ns >> 1) + col] = v.x;
+                            tile[(row + 1) * (ns >> 1) + col] = v.y;
+                        }
+                    } else if (last) {
                         if (col < N) {
                             if (b0 + row < args.B) args.out[((long)m * args.B + b0 + row) * N + col] = v.x;
                             if (b0 + row + 1 < args.B) args.out[((long)m * args.B + b0 + row + 1) * N + col] = v.y;
@@ -220,6 +247,12 @@ __global__ __launch_bounds__(kBf16Threads) void population_mlp_forward_shared_bf
         }
         if (!last) __syncthreads();
     }
+    if constexpr (kLoss) {
+        __syncthreads();
+        const bool odd = args.layers & 1;  // the buffer the last layer stored to
+        shared_loss_phase<BT>(reinterpret_cast<const float*>(odd ? buf1 : buf0), (odd ? stride1 : stride0) >> 1,
+                              reinterpret_cast<float*>(odd ? buf0 : buf1), m, b0 / BT, args, largs);
+    }
 }
 
 // Rows per batch tile, from the widths alone. 32 for every stack: measured
@@ -233,6 +266,13 @@ static int bf16_batch_tile(const int* width, int layers) {
     return 32;
 }
 
+// The loss layout's tile: 32 rows as above, except where a very wide last
+// layer's fp32 row next to a wide input no longer fits a CU's LDS at 32 rows
+// (more than 160 KB, e.g. 1024 -> 1024 -> 1024: 197,632 bytes); those take 16.
+int bf16_loss_batch_tile(const int* width, int layers) {
+    return bf16_loss_lds_bytes(width, layers, 32) <= kBf16LdsOneBlock ? 32 : 16;
+}
+
 int64_t population_mlp_forward_shared_bf16_batch_tile(std::vector<int64_t> widths) {
     int width[kMaxLayers + 1], act[kMaxLayers];
     const std::vector<int64_t> identity(widths.empty() ? 0 : widths.size() - 1, kActIdentity);
@@ -240,16 +280,27 @@ int64_t population_mlp_forward_shared_bf16_batch_tile(std::vector<int64_t> width
     return bf16_batch_tile(width, (int)widths.size() - 1);
 }
 
-template <int BT>
-static void launch_shared_bf16(const SharedForwardArgs& args, size_t lds_bytes, hipStream_t stream) {
+template <int BT, bool kLoss>
+static void launch_shared_bf16(const SharedForwardArgs& args, const SharedLossArgs& largs, size_t lds_bytes,
+                               hipStream_t stream) {
     static bool attr_set = false;
     if (!attr_set) {
-        allow_max_dynamic_lds(reinterpret_cast<const void*>(&population_mlp_forward_shared_bf16_kernel<BT>));
+        allow_max_dynamic_lds(reinterpret_cast<const void*>(&population_mlp_forward_shared_bf16_kernel<BT, kLoss>));
         attr_set = true;
     }
     const int grid = (args.blocks + kXcds - 1) / kXcds * kXcds;
-    hipLaunchKernelGGL(population_mlp_forward_shared_bf16_kernel<BT>, dim3(grid), dim3(kBf16Threads), lds_bytes,
-                       stream, args);
+    hipLaunchKernelGGL((population_mlp_forward_shared_bf16_kernel<BT, kLoss>), dim3(grid), dim3(kBf16Threads),
+                       lds_bytes, stream, args, largs);
+}
+
+// K17's launch: `args` as for the forward (out unused), `bt` from bf16_loss_batch_tile.
+void launch_shared_loss_bf16(const SharedForwardArgs& args, const SharedLossArgs& largs, int bt, hipStream_t stream) {
+    const size_t lds_bytes = bf16_loss_lds_bytes(args.width, args.layers, bt);
+    if (bt == 32) {
+        launch_shared_bf16<32, true>(args, largs, lds_bytes, stream);
+    } else {
+        launch_shared_bf16<16, true>(args, largs, lds_bytes, stream);
+    }
 }
 
 // `batch_tile` 0 takes the rule above; 32 or 64 overrides it (for measuring
@@ -288,10 +339,11 @@ torch::Tensor population_mlp_forward_shared_bf16(torch::Tensor params, torch::Te
     args.layers = (int)layers;
     args.has_bias = has_bias ? 1 : 0;
     auto stream = at::cuda::getCurrentCUDAStream();
+    const SharedLossArgs no_loss{};
     if (bt == 64) {
-        launch_shared_bf16<64>(args, lds_bytes, stream);
+        launch_shared_bf16<64, false>(args, no_loss, lds_bytes, stream);
     } else {
-        launch_shared_bf16<32>(args, lds_bytes, stream);
+        launch_shared_bf16<32, false>(args, no_loss, lds_bytes, stream);
     }
     return out;
 }

@@ -29,6 +29,7 @@ setup(
                 os.path.join(SRC, "policy_forward_recurrent.hip"),
                 os.path.join(SRC, "policy_forward_shared.hip"),
                 os.path.join(SRC, "policy_forward_shared_bf16.hip"),
+                os.path.join(SRC, "policy_loss_shared.hip"),
                 os.path.join(SRC, "rollout.hip"),
                 os.path.join(SRC, "rollout_v7.hip"),
                 os.path.join(SRC, "rollout_m7.hip"),
