@@ -1470,7 +1470,7 @@ class Problem(TensorMakerMixin, Serializable):
         return {
             "gradients": grads,
             "num_solutions": total_popsize,
-            "mean_eval": torch.nanmean(fitnesses),  # 0-dim tensor: no host sync
+            "mean_eval": ops.nanmean_1d(fitnesses),  # 0-dim tensor: no host sync
         }
 
     def _eval_shard_batch(self, batch: "SolutionBatch"):
@@ -1574,7 +1574,7 @@ class Problem(TensorMakerMixin, Serializable):
         return {
             "gradients": grads,
             "num_solutions": total,
-            "mean_eval": torch.nanmean(all_fit),  # 0-dim tensor: no host sync
+            "mean_eval": ops.nanmean_1d(all_fit),  # 0-dim tensor: no host sync
         }
 
     def _sample_and_compute_gradients_sharded(
@@ -1622,15 +1622,19 @@ class Problem(TensorMakerMixin, Serializable):
                 # bandwidth-bound (measured 82 vs 69 ms/gen at 50 GB).
                 and local_popsize * self._solution_length * 4 <= (1 << 30)
             )
+            # the batch's evals are all NaN already (forgotten by
+            # `_get_cached_grad_batch`, or just allocated): `access_values`
+            # need not launch the same fill again
+            values_out = batch.access_values(keep_evals=True)
             with record_range("sample"):
                 if use_overlap:
-                    self._sample_with_pregen(distribution, batch.access_values(), seed, rank * dirs_local, dirs_local)
+                    self._sample_with_pregen(distribution, values_out, seed, rank * dirs_local, dirs_local)
                     # pre-generate NEXT generation's noise on the side
                     # stream; it runs underneath the evaluation below and
                     # the gradient all-reduce after it
                     self._schedule_pregen(dirs_local, rank * dirs_local, self._peek_spmd_seed(1))
                 else:
-                    distribution.fill_counter_addressed(batch.access_values(), seed=seed, row_offset=rank * dirs_local)
+                    distribution.fill_counter_addressed(values_out, seed=seed, row_offset=rank * dirs_local)
             with record_range("evaluate"):
                 self._eval_shard_batch(batch)
             round_values.append(batch._values)

@@ -52,6 +52,8 @@ __all__ = [
     "unfused_generation_tail",
     "fused_tail_for",
     "GAUSSIAN_CLIPUP_UPDATE_MAX_LENGTH",
+    "nanmean_1d",
+    "NANMEAN_1D_MAX_LENGTH",
     "fused_adam_step_",
     "pareto_ranks",
     "domination_counts",
@@ -444,6 +446,27 @@ def gaussian_clipup_update(
     if stdev_min is not None or stdev_max is not None or stdev_max_change is not None:
         new_sigma = modify_tensor(sigma, new_sigma, lb=stdev_min, ub=stdev_max, max_change=stdev_max_change)
     return new_mu, new_sigma
+
+
+# ============================================================================
+# K2b — the generation's mean evaluation
+# ============================================================================
+
+NANMEAN_1D_MAX_LENGTH = 8192  # one block; kNanmeanMaxLength of es_kernels.hip
+
+
+def nanmean_1d(x: torch.Tensor) -> torch.Tensor:
+    """``torch.nanmean(x)`` as a 0-dim tensor, no host sync.
+
+    A dense 1-D fp32 ROCm vector of up to NANMEAN_1D_MAX_LENGTH elements
+    under the fused generation tail takes ONE kernel launch in place of
+    torch's six (isnan, logical_not, a cast, count, nansum, division); the nansum is
+    added in the order of torch's own reduction, so the bits are torch's.
+    Anything else is `torch.nanmean` itself."""
+    mod = fused_tail_for(x)
+    if mod is not None and x.dim() == 1 and x.is_contiguous() and 1 <= x.numel() <= NANMEAN_1D_MAX_LENGTH:
+        return mod.nanmean_1d(x)
+    return torch.nanmean(x)
 
 
 # ============================================================================

@@ -62,6 +62,8 @@ void cma_update_c(torch::Tensor C, torch::Tensor Y, torch::Tensor w, torch::Tens
                   torch::Tensor wsum, double c1, double cmu, double cc);
 void potrf_tile(torch::Tensor A, torch::Tensor info);
 torch::Tensor fused_rank(torch::Tensor fitnesses, int64_t method, bool higher_better);
+torch::Tensor nanmean_1d(torch::Tensor x);
+int64_t nanmean_1d_max_length();
 torch::Tensor domination_counts(torch::Tensor utils);
 torch::Tensor pareto_ranks(torch::Tensor utils, int64_t min_assigned);
 std::vector<torch::Tensor> mapelites_assign(torch::Tensor grid, torch::Tensor feats, torch::Tensor utils);
@@ -222,6 +224,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "K5b: in-LDS Cholesky of one <=128x128 SPD diagonal panel (in place, device info flag)");
     m.def("fused_rank", &ea::fused_rank,
           "K2: fused bitonic ranking + utility map (centered/linear/nes) in one launch");
+    m.def("nanmean_1d", &ea::nanmean_1d,
+          "K2b: torch.nanmean of a dense fp32 vector of 1..nanmean_1d_max_length() elements in one launch, with "
+          "torch's bits; returns a 0-dim fp32 tensor",
+          py::arg("x"));
+    m.def("nanmean_1d_max_length", &ea::nanmean_1d_max_length, "longest vector nanmean_1d accepts");
     m.def("domination_counts", &ea::domination_counts, "K7: NSGA-II domination counts (no N x N matrix)");
     m.def("pareto_ranks", &ea::pareto_ranks, "K7: NSGA-II non-dominated sorting by front peeling",
           py::arg("utils"), py::arg("min_assigned") = 0);

@@ -807,4 +807,128 @@ torch::Tensor fused_rank(torch::Tensor fitnesses, int64_t method, bool higher_be
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// K2b: torch.nanmean of a dense fp32 vector (the generation's `mean_eval`) in
+// ONE launch of one block, with the bits of torch's six: isnan (x != x),
+// logical_not, the cast of that mask to int64, its int64 sum, the fp32
+// nansum, one division.
+//
+// Only the nansum has an order to keep. It is ATen's reduce_kernel for a
+// contiguous 1-D fp32 input (setReduceConfig with vt0 = 4, input_vec_size = 4),
+// which for 1 <= n <= 8192 is a single block of `width` x 1 threads and no
+// global stage:
+//   n <  128: width = last_pow2(n) (at most 64). Thread t adds the elements
+//             t + m·width, m = 0, 1, ..: element m goes to accumulator m % 4.
+//   n >= 128: width = min(last_pow2(n / 4), 512), 16-byte vector loads. If
+//             the vector starts `shift` elements past a 16-byte boundary,
+//             threads shift..3 first add element t - shift to accumulator 0
+//             and the rest begins at the boundary, 4 - shift elements in.
+//             Thread t then adds the 4-vectors t, t + width, ..: component i
+//             to accumulator i. The elements behind the last whole vector go
+//             one each to accumulator 0 of threads 0, 1, 2.
+//   Every accumulator starts at 0, a NaN adds 0, and the four combine as
+//   ((a0 + a1) + a2) + a3. Across threads: while more than 64 values are
+//   left, an LDS tree halves them (thread t takes t + offset, offset =
+//   width/2 .. 64); then a shfl_down tree with RISING offsets 1, 2, ..
+//   (ATen's order under ROCm) leaves the sum on thread 0.
+// The count of non-NaN elements is an integer and has no order: every thread
+// counts the elements it adds.
+// ---------------------------------------------------------------------------
+
+constexpr int kNanmeanThreads = 512;
+// The longest vector taken and tested (fused_rank's bound). ATen's single
+// 512-wide block goes on unchanged beyond it; its stage over several blocks
+// begins only at 256 values per thread.
+constexpr int64_t kNanmeanMaxLength = 8192;
+
+// acc + x as NanSumOps::reduce adds it, counting x when it is no NaN
+__device__ __forceinline__ float nansum_add(float acc, float x, int& valid) {
+    const bool is_nan = x != x;
+    valid += is_nan ? 0 : 1;
+    return acc + (is_nan ? 0.0f : x);
+}
+
+__global__ __launch_bounds__(kNanmeanThreads) void nanmean_1d_kernel(const float* __restrict__ x,
+                                                                     float* __restrict__ out, int n, int width,
+                                                                     bool vectorized) {
+#pragma clang fp contract(off)
+    __shared__ float shared[kNanmeanThreads];
+    __shared__ int valid_total;
+    const int tid = threadIdx.x;
+    if (tid == 0) valid_total = 0;
+
+    int valid = 0;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (tid < width) {
+        if (vectorized) {
+            const int shift = (int)((reinterpret_cast<uintptr_t>(x) % 16) / sizeof(float));
+            const float* data = x;
+            int end = n;
+            if (shift > 0) {
+                if (tid >= shift && tid < 4) acc[0] = nansum_add(acc[0], x[tid - shift], valid);
+                data = x + (4 - shift);
+                end = n - (4 - shift);
+            }
+            for (int idx = tid; idx * 4 + 3 < end; idx += width) {
+                const float4 v = *reinterpret_cast<const float4*>(data + idx * 4);
+                acc[0] = nansum_add(acc[0], v.x, valid);
+                acc[1] = nansum_add(acc[1], v.y, valid);
+                acc[2] = nansum_add(acc[2], v.z, valid);
+                acc[3] = nansum_add(acc[3], v.w, valid);
+            }
+            const int tail = end - end % 4 + tid;
+            if (tail < end) acc[0] = nansum_add(acc[0], data[tail], valid);
+        } else {
+            int idx = tid;
+            for (; idx + 3 * width < n; idx += 4 * width) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = nansum_add(acc[i], x[idx + i * width], valid);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (idx < n) acc[i] = nansum_add(acc[i], x[idx], valid);
+                idx += width;
+            }
+        }
+    }
+    float v = ((acc[0] + acc[1]) + acc[2]) + acc[3];
+
+    if (width > kWaveSize) {
+        shared[tid] = v;
+        for (int offset = width / 2; offset >= kWaveSize; offset >>= 1) {
+            __syncthreads();
+            if (tid < offset) {
+                v = v + shared[tid + offset];
+                shared[tid] = v;
+            }
+        }
+    }
+    __syncthreads();
+    for (int offset = kWaveSize / 2; offset > 0; offset >>= 1) valid += __shfl_down(valid, offset, kWaveSize);
+    if ((tid & (kWaveSize - 1)) == 0) atomicAdd(&valid_total, valid);
+    const int wave_width = width < kWaveSize ? width : kWaveSize;
+    for (int offset = 1; offset < wave_width; offset <<= 1) v = v + __shfl_down(v, offset, kWaveSize);
+    __syncthreads();
+    if (tid == 0) *out = v / (float)valid_total;
+}
+
+int64_t nanmean_1d_max_length() { return kNanmeanMaxLength; }
+
+torch::Tensor nanmean_1d(torch::Tensor x) {
+    check_primary(x, "x", 1);
+    TORCH_CHECK(x.scalar_type() == torch::kFloat32, "nanmean_1d expects float32, got ", x.scalar_type());
+    const int64_t n = x.numel();
+    TORCH_CHECK(n >= 1 && n <= kNanmeanMaxLength, "nanmean_1d supports 1 <= n <= ", kNanmeanMaxLength, ", got ", n);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr<float>()) % sizeof(float) == 0, "x must be 4-byte aligned");
+    // ATen's block width for this shape (set_block_dimension with dim1 = 1)
+    const bool vectorized = n >= 128;
+    const int64_t dim0 = vectorized ? n / 4 : n;
+    int width = 1;
+    while (2 * width <= dim0 && 2 * width <= kNanmeanThreads) width *= 2;
+    auto out = torch::empty({}, x.options());
+    hipLaunchKernelGGL(nanmean_1d_kernel, dim3(1), dim3(kNanmeanThreads), 0, at::cuda::getCurrentCUDAStream(),
+                       x.data_ptr<float>(), out.data_ptr<float>(), (int)n, width, vectorized);
+    return out;
+}
+
 }  // namespace ea
